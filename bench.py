@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: leapfrog-steps/sec at 1024 chains per GPU (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: one C-ABI call that runs `--traj` whole trajectories
 (momentum draw, H, L leapfrog steps, H, Metropolis, sample write-out) for every chain of this rank.  Inputs are
@@ -10,8 +10,13 @@ already runs under torch.distributed.run; every rank owns its own block of chain
 collective): weak scaling, value = all ranks' chain-steps / max-over-ranks time.
 
 Rank 0 prints ONE JSON line (contract in the task description).  `value` is the primary workload (cfg2: BASELINE
-config 2, the 1024-chain headline).  At N = 1 the default run adds `"secondary"`: BASELINE.json's second north-star
-target (D=100 explicit RMHMC at 1024 chains) and configs 3 / 4, each with its own `roofline` and `cpu_baseline`.
+config 2, the 1024-chain headline).  A plain run measures that workload alone: set-up, W warm-up steps, K timed steps,
+then from those steps' own samples and HIP events the roofline, acceptance and ESS/s (at N > 1 also the samples' gather
+for a workload that has one), and the line.  `--full` adds everything else: the untimed continuation steps behind the
+ESS/s of workloads whose step is one or two trajectories, the timing through hamiltorch_amd.sample() (`api_ms_per_step`), the CPU
+baseline (`cpu_baseline`) and, at N = 1, `"secondary"`: BASELINE.json's second north-star target (D=100 explicit RMHMC
+at 1024 chains) and configs 3 / 4, each with its own `roofline` and `cpu_baseline`; at N > 1 the same target on every
+rank (weak and strong scaling).  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs).
 Every `roofline` carries the SURVEY 8(d) model fraction AND `physical` (counter HBM GB/s, SIMDs occupied, matrix-pipe
 busy share: from the committed rocprofv3 PMC passes in profiles/physical.json, collected with tools/physical.sh).
 
@@ -58,7 +63,39 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true", help="primary workload only")
     ap.add_argument("--no-api", action="store_true", help="skip the timing through hamiltorch_amd.sample()")
     ap.add_argument("--sweep", action="store_true", help="also print a chain-count sweep (stderr)")
+    ap.add_argument("--full", action="store_true", help="also the API timing, the CPU baseline and the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (rank 0's chains)")
     return ap.parse_args()
+
+
+DUMP_LIMIT = 64 << 20          # bytes of .npy files in all
+
+
+def dump_outputs(w, d):
+    """What the caller of the timed path receives from its last step, as DIR/<name>.npy (float64 stays float64, every other
+    dtype becomes float32): `samples` - the stored rows [T + 1, C, D] - and `final_state` - the chains' states [C, D] - where
+    the workload has them.  Not dumped: the per-chain rejection counts, which the workloads accumulate over all timed steps rather
+    than the last one (the samples carry the decisions: a rejected trajectory repeats the row before it).  The inputs are seeded,
+    so equal arguments give equal inputs.  Past DUMP_LIMIT bytes in all each
+    array keeps a fixed seeded sample of its flat elements, in index order, and the indices go to <name>_index.npy."""
+    import numpy as np
+    outs = {name: getattr(w, attr, None) for name, attr in (("samples", "samples"), ("final_state", "cur"))}
+    outs = {name: t for name, t in outs.items() if isinstance(t, torch.Tensor)}
+    if not outs:
+        raise SystemExit("bench.py: --dump-outputs: workload %s keeps no output tensors" % type(w).__name__)
+    total = sum(t.numel() * (8 if t.dtype == torch.float64 else 4) for t in outs.values())
+    budget = DUMP_LIMIT - (1 << 16)             # (room for the .npy headers)
+    os.makedirs(d, exist_ok=True)
+    for name, t in outs.items():
+        a = t.detach().cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        if total > budget:
+            # values + float64 indices: at most 4 + 8 bytes per kept float32 element, 8 + 8 per float64 one
+            k = int(a.size * budget // (3 * total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 
@@ -135,7 +172,9 @@ def main():
     # HIP event pair around the dominant kernel, on its stream, live in the timed region: every launch for the workloads with
     # several launches per step; every 4th for cfg2, where a pair (two barrier packets) is 3 % of a 0.19 ms step
     dt, call_ms, prof_ms, prof_n = measure(w, a.steps, a.warmup, world, dist, dev, 4 if a.workload == "cfg2" else 1)
-    res = result_of(w, W, dt, call_ms, prof_ms, prof_n, a.steps, a.warmup, world)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(w, a.dump_outputs)
+    res = result_of(w, W, dt, call_ms, prof_ms, prof_n, a.steps, a.warmup, world, ess_extra=a.full)
     gather_ms = None
     if hasattr(w, "gather"):            # the path's only collective, outside the timed region
         torch.cuda.synchronize()
@@ -151,10 +190,10 @@ def main():
             assert gathered.shape[1] == w.C * world
         del gathered
 
-    # --gpus N > 1 (the driver's scaling runs): the SECOND north-star target on every rank as well - D = 100 explicit RMHMC at
+    # --gpus N > 1 --full (the driver's scaling runs): the SECOND north-star target on every rank as well - D = 100 explicit RMHMC at
     # 1024 chains per GPU (cfg5) - and the path's only collective, the gather of its samples to rank 0 (after the timed region)
     res5 = res5s = None
-    if world > 1 and a.workload == "cfg2" and not a.no_secondary and a.chains is None and a.traj is None:
+    if world > 1 and a.full and a.workload == "cfg2" and not a.no_secondary and a.chains is None and a.traj is None:
         del w
         torch.cuda.empty_cache()
         w5 = Cfg5(dev, None, None, chain_offset=rank * Cfg5.chains)
@@ -197,14 +236,14 @@ def main():
             out["gather_ms"] = gather_ms
             out["config"]["parallelism"] += "; one gather of samples[%d, %d, %d] per rank to rank 0 after the timed region" % (
                 w.T + 1, w.C, W.D)
-        if hasattr(w, "api_call") and world == 1 and not a.no_api:
+        if hasattr(w, "api_call") and world == 1 and a.full and not a.no_api:
             api_ms, api_sync_ms = api_timing(w, a.steps, a.warmup)
             out["api_ms_per_step"] = api_ms
             out["api_value"] = w.units_per_step() / (api_ms * 1e-3)
             out["api_sync_ms"] = api_sync_ms
             out["api_note"] = "api_ms_per_step: the same K steps through hamiltorch_amd.sample() in the headline's bracket (route " \
                               "selection, sample-tensor allocation, the returned list); api_sync_ms: one call + synchronize, median of 5"
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             cb = w.cpu_baseline(a.cpu_seconds)
             if cb is not None:
                 cb.setdefault("host_cores_available", os.cpu_count())
@@ -216,7 +255,7 @@ def main():
                     out["ess_per_sec_vs_cpu_baseline"] = res["ess_per_sec"] / cb["ess_per_sec"]
         if res5 is not None:
             out["secondary"] = [res5] + ([res5s] if res5s is not None else [])
-        if world == 1 and a.workload == "cfg2" and not a.no_secondary and a.chains is None and a.traj is None:
+        if world == 1 and a.full and a.workload == "cfg2" and not a.no_secondary and a.chains is None and a.traj is None:
             del w
             torch.cuda.empty_cache()
             out["secondary"] = secondary(dev, a)

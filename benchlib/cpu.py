@@ -69,8 +69,11 @@ def cpu_baseline_procs(key, seconds, rounds=3, init_file=None):
     of start states (worker i of a round starts from row i mod k) - the device's burned-in chains, so that both sides of an ESS ratio
     measure mixing from the same place rather than the distance from a common starting point."""
     import subprocess
-    avail, procs = _usable_cores()
-    procs = max(1, min(procs, int(os.environ.get("HTA_BENCH_CPU_PROCS", "64"))))
+    avail, usable = _usable_cores()
+    # at most 15 workers by default: each imports the ROCm build of torch, and with the parent, which holds the device, a node then
+    # has at most 16 processes with the GPU runtime loaded.  (Records before this cap used 16 workers on 16 usable cores: on such a
+    # host `value` is now ~15/16 of theirs; `workers_cap` says when the cap, not the host, set the count.)
+    procs = max(1, min(usable, int(os.environ.get("HTA_BENCH_CPU_PROCS", "15"))))
     env = dict(os.environ, OMP_NUM_THREADS="1", MKL_NUM_THREADS="1", HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="",
                PYTHONDONTWRITEBYTECODE="1")
     from hamiltorch_amd.ess import ess_min, rhat_max
@@ -123,7 +126,9 @@ def cpu_baseline_procs(key, seconds, rounds=3, init_file=None):
                          "process start-up%s" % (procs, res[0]["n"], L, res[0]["impl"], dt, wall,
                                                  "; median of %d such rounds" % rounds if rounds > 1 else ""),
                "per_core": steps / dt / procs_ok, "samples_per_s": sum(r["n"] for r in res) / dt,
-               "samples_per_s_per_core": sum(r["n"] for r in res) / dt / procs_ok, "acceptance": sum(r["acc"] for r in res) / procs_ok, "host_cores_available": avail, "host_cores_usable": procs}
+               "samples_per_s_per_core": sum(r["n"] for r in res) / dt / procs_ok, "acceptance": sum(r["acc"] for r in res) / procs_ok, "host_cores_available": avail, "host_cores_usable": usable}
+        if procs < usable:
+            out["workers_cap"] = procs
         if failed:
             out["workers_failed_causes"] = causes
         if "samples" in res[0]:

@@ -67,8 +67,9 @@ def measure(w, steps, warmup, world, dist, dev, profile_every=1):
     return dt, call_ms, prof_ms, prof_n
 
 
-def result_of(w, W, dt, call_ms, prof_ms, prof_n, steps, warmup, world):
-    """The per-workload record: value, roofline (+ physical), acceptance, ESS/s."""
+def result_of(w, W, dt, call_ms, prof_ms, prof_n, steps, warmup, world, ess_extra=True):
+    """The per-workload record: value, roofline (+ physical), acceptance, ESS/s.  `ess_extra=False` (a plain bench.py run): no
+    untimed continuation steps for the ESS of workloads whose step is one or two trajectories - their `ess_per_sec` is NaN."""
     acc = w.check()
     units = w.units_per_step() * steps * world
     if isinstance(w, Cfg2):
@@ -107,7 +108,7 @@ def result_of(w, W, dt, call_ms, prof_ms, prof_n, steps, warmup, world):
     if w.T >= 8 and not getattr(W, "ess_extra_steps", 0):
         used = w.samples[1:, :, :ESS_DIMS]
         ess, ess_draws, rhat = ess_min(used), [int(used.shape[0]), int(used.shape[1])], rhat_max(used)
-    elif getattr(W, "ess_extra_steps", 0) and w.samples is not None and os.environ.get("HTA_BENCH_ESS_EXTRA", "1") != "0":
+    elif getattr(W, "ess_extra_steps", 0) and ess_extra and w.samples is not None and os.environ.get("HTA_BENCH_ESS_EXTRA", "1") != "0":
         # workloads whose step is one or two trajectories (the published-model runs, funnel-rmhmc): an UNTIMED run of consecutive steps
         # after the measurement - the chain state travels from step to step - supplies the draws; ESS / s = ESS of those draws / (their
         # steps x the measured time per step)

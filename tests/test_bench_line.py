@@ -161,3 +161,31 @@ def test_cpu_baseline_rounds_report_the_median_of_each_number():
     nan = float("nan")
     out = pick_round([{"value": 1.0, "ess_per_sec": nan}, {"value": 2.0, "ess_per_sec": 4.0}, {"value": 3.0, "ess_per_sec": 5.0}])
     assert out["value"] == 2.0 and out["ess_per_sec"] == 4.0 and "ess_per_sec_rounds" not in out      # a round without an estimate: the median round's own
+
+
+def test_dump_outputs_writes_the_last_step_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: samples and final states as float32 / float64 .npy files; past DUMP_LIMIT a seeded sample of the elements with
+    their indices - the same elements on every run, and the whole dump under the limit."""
+    import types
+
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    w = types.SimpleNamespace(samples=torch.randn(11, 64, 3, generator=g), cur=torch.randn(64, 3, generator=g, dtype=torch.float64))
+    bench.dump_outputs(w, str(tmp_path / "small"))
+    s, f = np.load(tmp_path / "small" / "samples.npy"), np.load(tmp_path / "small" / "final_state.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, w.samples.numpy())
+    assert f.dtype == np.float64 and np.array_equal(f, w.cur.numpy())
+    assert sorted(os.listdir(tmp_path / "small")) == ["final_state.npy", "samples.npy"]
+    w = types.SimpleNamespace(samples=torch.randn(101, 1024, 3, generator=g), cur=torch.randn(1024, 3, generator=g, dtype=torch.float64))
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 1 << 19)
+    for d in ("big1", "big2"):
+        bench.dump_outputs(w, str(tmp_path / d))
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["final_state.npy", "final_state_index.npy", "samples.npy", "samples_index.npy"]
+        assert sum(os.path.getsize(tmp_path / d / n) for n in files) <= bench.DUMP_LIMIT
+    for n in ("samples", "final_state"):
+        v, i = np.load(tmp_path / "big1" / (n + ".npy")), np.load(tmp_path / "big1" / (n + "_index.npy"))
+        assert 0 < v.size < getattr(w, "samples" if n == "samples" else "cur").numel() and np.all(np.diff(i) > 0)
+        assert np.array_equal(v, getattr(w, "samples" if n == "samples" else "cur").numpy().reshape(-1)[i.astype(np.int64)])
+        assert np.array_equal(v, np.load(tmp_path / "big2" / (n + ".npy")))

@@ -213,6 +213,27 @@ def test_bench_gpus_flag_launches_the_ranks_itself(ht):
     assert r2.returncode != 0 and "WORLD_SIZE" in (r2.stderr + r2.stdout)
 
 
+def test_bench_dump_outputs_are_the_last_timed_steps(ht, tmp_path):
+    """`bench.py --dump-outputs DIR` on the headline workload: samples [T + 1, C, 3] and final states [C, 3] as float32, the final
+    states equal to the last stored row, and the dump is that of the LAST timed step - step k draws with seed + k, so two runs whose
+    last step has the same k (2 timed after 1 warm-up, 1 after 2) write identical files and a run that ends one step later does not."""
+    def run(steps, warmup, d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--traj", "50", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads(r.stdout.strip().splitlines()[-1])
+        assert j["steps"] == steps and j["warmup"] == warmup and j["ms_per_step"] > 0 and "secondary" not in j
+        assert sorted(os.listdir(tmp_path / d)) == ["final_state.npy", "samples.npy"]
+        return np.load(tmp_path / d / "samples.npy"), np.load(tmp_path / d / "final_state.npy")
+    s, f = run(2, 1, "a")
+    assert s.dtype == np.float32 and s.shape == (51, 1024, 3) and np.isfinite(s).all()
+    assert f.dtype == np.float32 and f.shape == (1024, 3) and np.array_equal(f, s[-1])
+    s2, f2 = run(1, 2, "b")
+    assert np.array_equal(s, s2) and np.array_equal(f, f2)
+    s3, _ = run(3, 1, "c")
+    assert not np.array_equal(s[1:], s3[1:])
+
+
 def _free_port():
     import socket
     so = socket.socket()
@@ -222,11 +243,11 @@ def _free_port():
     return port
 
 
-@pytest.mark.parametrize("extra", [[], ["--workload", "cfg5", "--traj", "4"]])
+@pytest.mark.parametrize("extra", [["--full"], ["--workload", "cfg5", "--traj", "4"], []])
 def test_drivers_eight_rank_command_line_prints_the_compact_line(ht, extra):
     """The exact launcher line of the driver's scaling run - `python -m torch.distributed.run --nnodes=1 --nproc-per-node 8
-    --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 --steps K --warmup W` - for the default workload (cfg2 weak
-    scaling) and for `--workload cfg5` (cfg3 sharded, with the gather): eight ranks share this box's one GPU over gloo
+    --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 --steps K --warmup W` - plain (cfg2 weak scaling alone), with --full
+    (cfg2 and the secondary targets) and for `--workload cfg5` (cfg3 sharded, with the gather): eight ranks share one GPU over gloo
     (HTA_BENCH_BACKEND; RCCL needs eight devices), so that the first real 8-GPU run cannot fail on plumbing.  The LAST stdout
     line must be the < 4 KB record with n_gpus / ranks_seen / rank_devices / collective_backend / gather_ms."""
     env = dict(os.environ, HTA_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
@@ -244,12 +265,14 @@ def test_drivers_eight_rank_command_line_prints_the_compact_line(ht, extra):
     assert j["collective_backend"] == "gloo" and j["launcher"] == "torch.distributed.run"        # "rccl" on the driver's node
     assert j["scaling"] == "weak" and j["config"]["chains_total"] == 8 * j["config"]["chains_per_gpu"] == 8192
     assert j["value"] > 0 and "roofline" in j and j["roofline"]["kernel"]
-    if extra:
+    if "--workload" in extra:
         assert j["gather_ms"] > 0 and j["config"]["workload"] == "cfg5"
+    elif not extra:         # the plain command: the headline alone
+        assert j["config"]["workload"] == "cfg2" and "gather_ms" not in j and "secondary" not in j
     else:
         assert j["config"]["workload"] == "cfg2" and "gather_ms" not in j
-        # round 4: the default multi-GPU line also carries the SECOND north-star target - D = 100 explicit RMHMC
-        # at 1024 chains per GPU on every rank - with the gather, so one scaling run yields both curves
+        # round 4: the multi-GPU line of a --full run also carries the SECOND north-star target - D = 100 explicit
+        # RMHMC at 1024 chains per GPU on every rank - with the gather, so one scaling run yields both curves
         s5 = j["secondary"][0]
         assert s5["key"] == "cfg5" and s5["n_gpus"] == 8 and s5["ranks_seen"] == 8 and s5["gather_ms"] > 0 and s5["value"] > 0
         assert s5["chains"] == 1024 and s5["kernel"].startswith("rmhmc_uvc2")
