@@ -34,6 +34,8 @@ __device__ __forceinline__ float cb_atan(float x) { return atanf(x); }
 __device__ __forceinline__ double cb_atan(double x) { return atan(x); }
 __device__ __forceinline__ float cb_erf(float x) { return erff(x); }
 __device__ __forceinline__ double cb_erf(double x) { return erf(x); }
+__device__ __forceinline__ float cb_erfc(float x) { return erfcf(x); }        // not 1 - erf: the tail erfc(9) = 4e-37 stays finite
+__device__ __forceinline__ double cb_erfc(double x) { return erfc(x); }
 __device__ __forceinline__ float cb_lgamma(float x) { return lgammaf(x); }
 __device__ __forceinline__ double cb_lgamma(double x) { return lgamma(x); }
 __device__ __forceinline__ float cb_abs(float x) { return fabsf(x); }
@@ -58,11 +60,15 @@ template <typename T> __device__ __forceinline__ T cb_sigmoid(T x) { return (T)1
 // log(1 + exp(x)) without overflow: max(x, 0) + log1p(exp(-|x|))
 template <typename T> __device__ __forceinline__ T cb_softplus(T x) { return fmax(x, (T)0) + cb_log1p(cb_exp(-cb_abs(x))); }
 template <typename T> __device__ __forceinline__ bool cb_isnan(T x) { return x != x; }
+// torch.xlogy: 0 where x == 0 (also at y = 0 and y = inf), NaN where y is NaN
+template <typename T> __device__ __forceinline__ T cb_xlogy(T x, T y) { return (y != y) ? y : (x == (T)0 ? (T)0 : x * cb_log(y)); }
 template <typename T> __device__ __forceinline__ bool cb_isinf(T x) { return cb_abs(x) == (T)__builtin_huge_val(); }
 
 // digamma: the recurrence up to x >= 6, then the asymptotic series (relative error < 1e-8 in double); reflection for x < 0.
+// At the pole 0 torch's value: -inf at +0, +inf at -0; NaN at the negative integers.
 template <typename T> __device__ inline T cb_digamma(T x) {
   double v = (double)x, r = 0.0;
+  if (v == 0.0) return (T)(__builtin_signbit(v) ? __builtin_huge_val() : -__builtin_huge_val());
   if (v <= 0.0) {
     if (v == floor(v)) return (T)__builtin_nan("");
     const double pi = 3.14159265358979323846;

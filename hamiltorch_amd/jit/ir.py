@@ -19,10 +19,13 @@ import numpy as np
 
 # op -> arity.  'f' ops produce floats, 'b' ops booleans.
 UNARY = ("neg", "exp", "log", "sqrt", "rsqrt", "tanh", "sigmoid", "log1p", "expm1", "sin", "cos", "abs", "sign", "erf",
-         "recip", "softplus", "floor", "ceil", "round", "trunc", "atan", "lgamma", "digamma", "detach")
-BINARY = ("add", "sub", "mul", "div", "pow", "max", "min")
+         "erfc", "recip", "softplus", "floor", "ceil", "round", "trunc", "atan", "lgamma", "digamma", "detach")
+BINARY = ("add", "sub", "mul", "div", "pow", "max", "min", "xlogy")
 COMPARE = ("gt", "ge", "lt", "le", "eq", "ne")
 BOOL = ("and", "or", "not", "isnan", "isinf")
+# leaves without operands: an input, a constant, and "finfo_max" - the largest finite value of the dtype the graph is evaluated /
+# emitted in (nan_to_num's default replacement of +inf), resolved by `evaluate` and emit.literal per dtype
+LEAVES = ("const", "bconst", "in", "finfo_max")
 
 _TWO_OVER_SQRT_PI = 2.0 / math.sqrt(math.pi)
 
@@ -39,6 +42,19 @@ def _erf(x):
         return np.vectorize(math.erf)(x)
 
 
+def _erfc(x):
+    try:
+        from scipy.special import erfc
+        return erfc(x)
+    except Exception:       # pragma: no cover
+        return np.vectorize(math.erfc)(x)
+
+
+def _xlogy(x, y):
+    """torch.xlogy: x log y, 0 where x == 0 (y = 0 and y = inf included), NaN where y is NaN."""
+    return np.where(np.isnan(y), y, np.where(x == 0, 0.0, x * np.log(y)))
+
+
 def _sp(name):
     def f(x):
         import scipy.special as sp
@@ -46,16 +62,30 @@ def _sp(name):
     return f
 
 
+def _digamma(x):
+    # torch's rule at the pole 0: -inf at +0, +inf at -0 (scipy agrees; written out so that the device helper has a stated model)
+    x = np.asarray(x)
+    return np.where(x == 0, -np.copysign(np.inf, x), _sp("digamma")(x))
+
+
 _NP_UNARY = {
     "neg": np.negative, "exp": np.exp, "log": np.log, "sqrt": np.sqrt, "rsqrt": lambda x: 1.0 / np.sqrt(x), "tanh": np.tanh,
     "sigmoid": lambda x: 1.0 / (1.0 + np.exp(-x)), "log1p": np.log1p, "expm1": np.expm1, "sin": np.sin, "cos": np.cos,
-    "abs": np.abs, "sign": np.sign, "erf": _erf, "recip": lambda x: 1.0 / x, "softplus": _softplus, "floor": np.floor,
-    "ceil": np.ceil, "round": np.round, "trunc": np.trunc, "atan": np.arctan, "lgamma": _sp("gammaln"), "digamma": _sp("digamma"),
+    "abs": np.abs, "sign": np.sign, "erf": _erf, "erfc": _erfc, "recip": lambda x: 1.0 / x, "softplus": _softplus, "floor": np.floor,
+    "ceil": np.ceil, "round": np.round, "trunc": np.trunc, "atan": np.arctan, "lgamma": _sp("gammaln"), "digamma": _digamma,
     "detach": lambda x: x,
 }
 _NP_BINARY = {"add": np.add, "sub": np.subtract, "mul": np.multiply, "div": np.divide, "pow": np.power, "max": np.maximum,
-              "min": np.minimum}
+              "min": np.minimum, "xlogy": _xlogy}
 _NP_COMPARE = {"gt": np.greater, "ge": np.greater_equal, "lt": np.less, "le": np.less_equal, "eq": np.equal, "ne": np.not_equal}
+
+
+def _folds(c1, c2):
+    """c1 * c2 may replace the two constant factors: finite and, unless a factor is zero, not zero."""
+    if c1 == "nan" or c2 == "nan":
+        return False
+    p = c1 * c2
+    return math.isfinite(p) and (p != 0.0 or c1 == 0.0 or c2 == 0.0)
 
 
 class Graph:
@@ -86,6 +116,10 @@ class Graph:
 
     def bconst(self, v):
         return self._new(("bconst", bool(v)))
+
+    def finfo_max(self):
+        """The largest finite value of the dtype the graph runs in (float32's or float64's)."""
+        return self._new(("finfo_max",))
 
     def is_const(self, i):
         return self.nodes[i][0] == "const"
@@ -181,10 +215,11 @@ class Graph:
                 return self.unary("neg", self.binary("mul", na[1], b))
             if nb[0] == "neg":
                 return self.unary("neg", self.binary("mul", a, nb[1]))
-            # c1 * (c2 * x) -> (c1 c2) * x
-            if ca and nb[0] == "mul" and self.is_const(nb[1]):
+            # c1 * (c2 * x) -> (c1 c2) * x, unless c1 c2 overflows or underflows (1e300 * 1e300 * x is not inf * x: at a zero
+            # derivative 0 * inf would be NaN)
+            if ca and nb[0] == "mul" and self.is_const(nb[1]) and _folds(na[1], self.cval(nb[1])):
                 return self.binary("mul", self.const(na[1] * self.cval(nb[1])), nb[2])
-            if cb and na[0] == "mul" and self.is_const(na[1]):
+            if cb and na[0] == "mul" and self.is_const(na[1]) and _folds(nb[1], self.cval(na[1])):
                 return self.binary("mul", self.const(nb[1] * self.cval(na[1])), na[2])
             if a == b and na[0] == "sqrt":
                 return na[1]
@@ -208,7 +243,10 @@ class Graph:
                 return self.unary("neg", a)
             if cb and nb[1] != 0.0 and nb[1] != "nan" and math.isfinite(nb[1]):
                 r = 1.0 / nb[1]
-                if r * nb[1] == 1.0 and math.isfinite(r):        # exact reciprocals only (powers of two ...): x / c stays a division otherwise
+                # exact reciprocals only (powers of two): x / c stays a division otherwise.  (r * c == 1 is not enough: 1/3 * 3 rounds
+                # to 1, but x - s * (1/3) contracts to an FMA on the device and the deviation of a constant input from its mean is
+                # 5.6e-17 instead of 0 - std's masked gradient at zero spread then sees a nonzero variance)
+                if math.frexp(abs(nb[1]))[0] == 0.5 and math.isfinite(r) and r != 0.0:
                     return self.binary("mul", a, self.const(r))
             if na[0] == "neg":
                 return self.unary("neg", self.binary("div", na[1], b))
@@ -231,19 +269,19 @@ class Graph:
                     return self.unary("recip", a)
                 if e == -0.5:
                     return self.unary("rsqrt", a)
-                if e == -2.0:
-                    return self.unary("recip", self.binary("mul", a, a))
                 if e == "nan":
                     return self.const(float("nan"))
-                if float(e).is_integer() and 2.0 < abs(e) <= 8.0:
-                    k, acc, base = int(abs(e)), None, a
+                if float(e).is_integer() and 2.0 <= abs(e) <= 8.0:
+                    # a negative power as a power of the reciprocal: (1/x)^k, not 1/x^k, whose derivative at x = 0 is
+                    # -(1/x^k)^2 * k x^(k-1) = -inf * 0 = NaN where torch has -k x^(-k-1) = -inf
+                    k, acc, base = int(abs(e)), None, (a if e > 0 else self.unary("recip", a))
                     while k:
                         if k & 1:
                             acc = base if acc is None else self.binary("mul", acc, base)
                         k >>= 1
                         if k:
                             base = self.binary("mul", base, base)
-                    return acc if e > 0 else self.unary("recip", acc)
+                    return acc
         elif op in ("max", "min"):
             if a == b:
                 return a
@@ -315,10 +353,26 @@ class Graph:
                 continue
             seen.add(i)
             n = self.nodes[i]
-            if n[0] in ("const", "bconst", "in"):
+            if n[0] in LEAVES:
                 continue
             stack.extend(n[1:])
         return sorted(seen)
+
+    def _differentiable(self, i):
+        """Whether an input reaches node i other than through a 'detach'."""
+        seen, stack = set(), [int(i)]
+        while stack:
+            j = stack.pop()
+            if j in seen:
+                continue
+            seen.add(j)
+            n = self.nodes[j]
+            if n[0] == "in":
+                return True
+            if n[0] in LEAVES or n[0] == "detach" or n[0] in COMPARE or n[0] in BOOL:
+                continue
+            stack.extend(n[2:] if n[0] == "sel" else n[1:])
+        return False
 
     def depends_on_input(self, i):
         return any(self.nodes[j][0] == "in" for j in self.reachable([i]))
@@ -337,7 +391,7 @@ class Graph:
                 continue
             n = self.nodes[i]
             op = n[0]
-            if op in ("const", "bconst", "in") or op in COMPARE or op in BOOL:
+            if op in LEAVES or op in COMPARE or op in BOOL:
                 continue
 
             def acc(x, v):
@@ -384,20 +438,38 @@ class Graph:
                 acc(n[1], self.mul(a, self.unary("sign", n[1])))
             elif op == "erf":
                 acc(n[1], self.mul(a, self.mul(self.const(_TWO_OVER_SQRT_PI), self.unary("exp", self.neg(self.mul(n[1], n[1]))))))
+            elif op == "erfc":
+                acc(n[1], self.mul(a, self.mul(self.const(-_TWO_OVER_SQRT_PI), self.unary("exp", self.neg(self.mul(n[1], n[1]))))))
             elif op == "lgamma":
                 acc(n[1], self.mul(a, self.unary("digamma", n[1])))
             elif op == "digamma":
-                raise Unsupported("derivative of digamma (a second derivative of lgamma)")
+                if self._differentiable(n[1]):
+                    raise Unsupported("derivative of digamma (a second derivative of lgamma)")
             elif op in ("sign", "floor", "ceil", "round", "trunc", "detach"):
                 pass
             elif op == "pow":
+                # torch's rules: d/dx = 0 where y == 0 (not 0 * x^-1 at x = 0); d/dy = 0 where x == 0 and y >= 0 (not x^y log 0)
                 x, y = n[1], n[2]
-                acc(x, self.mul(a, self.mul(y, self.binary("pow", x, self.sub(y, self.const(1.0))))))
+                dx = self.mul(a, self.mul(y, self.binary("pow", x, self.sub(y, self.const(1.0)))))
                 if not self.is_const(y):
-                    acc(y, self.mul(a, self.mul(i, self.unary("log", x))))
+                    dx = self.select(self.compare("eq", y, zero), zero, dx)
+                acc(x, dx)
+                if not self.is_const(y):
+                    x0 = self.boolean("and", self.compare("eq", x, zero), self.compare("ge", y, zero))
+                    acc(y, self.select(x0, zero, self.mul(a, self.mul(i, self.unary("log", x)))))
+            elif op == "xlogy":
+                # torch's rules: d/dx = log y, with y read as 1 where x == 0 and y <= 0; d/dy = x / y (NaN at x = y = 0)
+                x, y = n[1], n[2]
+                safe_y = self.select(self.boolean("and", self.compare("eq", x, zero), self.compare("le", y, zero)), self.const(1.0), y)
+                acc(x, self.mul(a, self.unary("log", safe_y)))
+                acc(y, self.mul(a, self.div(x, y)))
             elif op in ("max", "min"):
-                c = self.compare("ge" if op == "max" else "le", n[1], n[2])
-                acc(n[1], self.select(c, a, zero)); acc(n[2], self.select(c, zero, a))
+                # torch.maximum / torch.minimum: half to each operand at a tie, all to the larger (smaller) one otherwise; a NaN
+                # operand (neither < nor ==) passes the whole gradient to both
+                lose1 = self.compare("lt" if op == "max" else "gt", n[1], n[2])
+                lose2 = self.compare("gt" if op == "max" else "lt", n[1], n[2])
+                half = self.select(self.compare("eq", n[1], n[2]), self.mul(self.const(0.5), a), a)
+                acc(n[1], self.select(lose1, zero, half)); acc(n[2], self.select(lose2, zero, half))
             elif op == "sel":
                 acc(n[2], self.select(n[1], a, zero)); acc(n[3], self.select(n[1], zero, a))
             else:       # pragma: no cover
@@ -419,6 +491,8 @@ class Graph:
                     v = np.asarray(self.cval(i), dt)
                 elif op == "bconst":
                     v = np.asarray(n[1])
+                elif op == "finfo_max":
+                    v = np.asarray(np.finfo(dt).max, dt)
                 elif op == "in":
                     v = theta[..., n[1]].astype(dt)
                 elif op in _NP_UNARY:

@@ -184,6 +184,19 @@ class _Lowering:
                 out = np.expand_dims(out, d)
         return TV(out)
 
+    def extreme(self, op, x, dims, keepdim=False):
+        """amax / amin / max / min over `dims` with torch's backward: the gradient is split evenly over every entry equal to the
+        result (a pairwise fold of 'max' nodes would hand a 3-way tie 1/4, 1/4, 1/2).  The value is the extreme itself, exactly:
+        m + sum(x - m over the ties) / count with m detached (infinite m read as 0: the tied x carry it); NaN propagates."""
+        x = self.f(x)
+        m = self.reduce(op, x, dims, True)
+        hit = self.cmp("eq", x, m)
+        cnt = self.reduce("add", self.f(hit), dims, keepdim)
+        ms = self.un("detach", self.where(self.cmp("eq", self.un("abs", m), math.inf), 0.0, m))
+        dev = self.reduce("add", self.where(hit, self.bi("sub", x, ms), 0.0), dims, keepdim)
+        msk = ms if keepdim else TV(ms.ids.reshape(dev.shape))
+        return self.bi("add", msk, self.bi("div", dev, cnt))
+
     def matmul(self, a, b):
         a, b = self.f(a), self.f(b)
         A, B = a.ids, b.ids
@@ -458,13 +471,14 @@ def _build_table():
 
     @reg(*_ov("diag_embed"))
     def _diag_embed(L, x, offset=0, dim1=-2, dim2=-1):
-        if offset != 0 or (dim1, dim2) not in ((-2, -1),):
-            raise Unsupported("diag_embed with offset / dims")
         a = L.f(x).ids
-        n = a.shape[-1]
-        out = np.full(a.shape + (n,), L.g.const(0.0), np.int64)
-        for i in range(n):
-            out[..., i, i] = a[..., i]
+        nd = a.ndim + 1
+        if (dim1 % nd, dim2 % nd) != (nd - 2, nd - 1):         # (torch.diag(v, k) arrives as diag_embed(v, k, 0, 1))
+            raise Unsupported("diag_embed into dims other than the last two")
+        n = a.shape[-1] + abs(offset)
+        out = np.full(a.shape[:-1] + (n, n), L.g.const(0.0), np.int64)
+        for i in range(a.shape[-1]):
+            out[..., i + max(-offset, 0), i + max(offset, 0)] = a[..., i]
         return TV(out)
 
     @reg(*_ov("diag", "default"))
@@ -639,13 +653,24 @@ def _build_table():
     def _square(L, x):
         return L.bi("mul", x, x)
 
-    @reg(*_ov("maximum", "default"), *_ov("fmax", "default"), *_ov("max", "other"))
+    @reg(*_ov("maximum", "default"), *_ov("max", "other"))
     def _maximum(L, x, y):
         return L.bi("max", x, y)
 
-    @reg(*_ov("minimum", "default"), *_ov("fmin", "default"), *_ov("min", "other"))
+    @reg(*_ov("minimum", "default"), *_ov("min", "other"))
     def _minimum(L, x, y):
         return L.bi("min", x, y)
+
+    def _fmaxmin(op):
+        # fmax / fmin ignore a NaN operand; torch's backward gives the whole gradient to x where x >= y (x <= y) or y is NaN
+        def fn(L, x, y):
+            keep = _or(L, L.cmp(op, x, y), _isnan(L, y))
+            return L.where(keep, x, y)
+        return fn
+    for o in _ov("fmax", "default"):
+        T[o] = _fmaxmin("ge")
+    for o in _ov("fmin", "default"):
+        T[o] = _fmaxmin("le")
 
     for name, op in (("neg", "neg"), ("negative", "neg"), ("exp", "exp"), ("log", "log"), ("sqrt", "sqrt"), ("rsqrt", "rsqrt"),
                      ("tanh", "tanh"), ("sigmoid", "sigmoid"), ("log1p", "log1p"), ("expm1", "expm1"), ("sin", "sin"),
@@ -661,7 +686,7 @@ def _build_table():
 
     @reg(*_ov("erfc", "default"), *_ov("special_erfc", "default"))
     def _erfc(L, x):
-        return L.bi("sub", 1.0, L.un("erf", x))
+        return L.un("erfc", x)
 
     @reg(*_ov("log2", "default"))
     def _log2(L, x):
@@ -685,14 +710,15 @@ def _build_table():
 
     @reg(*_ov("sinh", "default"))
     def _sinh(L, x):
-        return L.bi("mul", L.bi("sub", L.un("exp", x), L.un("exp", L.un("neg", x))), 0.5)
+        # through expm1: (e^x - e^-x) / 2 cancels near 0
+        return L.bi("mul", L.bi("sub", L.un("expm1", x), L.un("expm1", L.un("neg", x))), 0.5)
 
     @reg(*_ov("softplus", "default"))
     def _softplus(L, x, beta=1.0, threshold=20.0):
-        # (beta x > threshold -> x in torch: a difference below exp(-threshold) = 2e-9, and the derivative stays finite here)
-        if beta == 1.0:
-            return L.un("softplus", x)
-        return L.bi("div", L.un("softplus", L.bi("mul", x, beta)), beta)
+        # torch switches to the identity where beta x > threshold (value and derivative)
+        bx = L.bi("mul", x, beta)
+        sp = L.un("softplus", bx) if beta == 1.0 else L.bi("div", L.un("softplus", bx), beta)
+        return L.where(L.cmp("gt", bx, threshold), x, sp)
 
     @reg(*_ov("log_sigmoid", "default"))
     def _log_sigmoid(L, x):
@@ -704,7 +730,7 @@ def _build_table():
 
     @reg(*_ov("relu", "default"))
     def _relu(L, x):
-        return L.bi("max", x, 0.0)
+        return L.where(L.cmp("le", x, 0.0), 0.0, x)         # derivative 1 strictly above 0; NaN passes with derivative 1 (torch)
 
     @reg(*_ov("leaky_relu", "default"))
     def _leaky(L, x, slope=0.01):
@@ -728,32 +754,46 @@ def _build_table():
 
     @reg(*_ov("hardtanh", "default"))
     def _hardtanh(L, x, lo=-1.0, hi=1.0):
-        return L.bi("min", L.bi("max", x, lo), hi)
+        # derivative 1 strictly inside (lo, hi), 0 at the bounds (torch's hardtanh_backward)
+        return L.where(L.cmp("le", x, lo), lo, L.where(L.cmp("ge", x, hi), hi, x))
 
+    # clamp with torch's clamp_backward masks: x gets the gradient on [lo, hi] (bounds included), lo where x < lo < hi, hi where
+    # x > hi or hi < lo (the result is then hi); nobody where an operand is NaN (the value is NaN) or x < lo == hi
     @reg(*_ov("clamp", "default", "Tensor"), *_ov("clip", "default"))
     def _clamp(L, x, lo=None, hi=None):
-        if lo is not None:
-            x = L.bi("max", x, lo)
-        if hi is not None:
-            x = L.bi("min", x, hi)
-        return x
+        x = L.f(x)
+        if lo is None and hi is None:
+            return x
+        if hi is None:
+            rest = L.un("detach", L.where(_isnan(L, x), x, lo))
+            return L.where(L.cmp("ge", x, lo), x, L.where(L.cmp("lt", x, lo), lo, rest))
+        if lo is None:
+            rest = L.un("detach", L.where(_isnan(L, x), x, hi))
+            return L.where(L.cmp("le", x, hi), x, L.where(L.cmp("gt", x, hi), hi, rest))
+        in_x = _and(L, L.cmp("ge", x, lo), L.cmp("le", x, hi))
+        to_lo = _and(L, L.cmp("lt", x, lo), L.cmp("lt", lo, hi))
+        to_hi = _or(L, L.cmp("gt", x, hi), L.cmp("lt", hi, lo))
+        rest = L.un("detach", L.where(_isnan(L, x), x, L.where(_isnan(L, lo), lo, hi)))
+        return L.where(in_x, x, L.where(to_lo, lo, L.where(to_hi, hi, rest)))
 
     @reg(*_ov("clamp_min", "default", "Tensor"))
     def _clamp_min(L, x, lo):
-        return L.bi("max", x, lo)
+        return _clamp(L, x, lo, None)
 
     @reg(*_ov("clamp_max", "default", "Tensor"))
     def _clamp_max(L, x, hi):
-        return L.bi("min", x, hi)
+        return _clamp(L, x, None, hi)
 
     @reg(*_ov("xlogy", "Tensor", "Scalar_Self", "Scalar_Other"))
     def _xlogy(L, x, y):
-        return L.where(L.cmp("eq", x, 0.0), 0.0, L.bi("mul", x, L.un("log", y)))
+        return L.bi("xlogy", x, y)          # (ir.py: the value and torch's derivative rules)
 
     @reg(*_ov("logaddexp", "default"))
     def _logaddexp(L, x, y):
+        # a two-term logsumexp (see _logsumexp): half of the gradient to each operand at a tie, as torch
         m = L.bi("max", x, y)
-        return L.bi("add", m, L.un("log1p", L.un("exp", L.un("neg", L.un("abs", L.bi("sub", x, y))))))
+        m = L.un("detach", L.where(_isinf(L, m), 0.0, m))
+        return L.bi("add", L.un("log", L.bi("add", L.un("exp", L.bi("sub", x, m)), L.un("exp", L.bi("sub", y, m)))), m)
 
     @reg(*_ov("addcmul", "default"))
     def _addcmul(L, x, a, b, value=1):
@@ -809,10 +849,11 @@ def _build_table():
 
     @reg(*_ov("nan_to_num", "default"))
     def _nan_to_num(L, x, nan=0.0, posinf=None, neginf=None):
-        big = 3.4028234663852886e38
-        y = L.where(_isnan(L, x), 0.0 if nan is None else nan, x)
-        y = L.bi("min", y, big if posinf is None else posinf)
-        return L.bi("max", y, -big if neginf is None else neginf)
+        # the default replacements of +-inf are the largest finite values of the dtype the code runs in; derivative 1 where x is finite
+        big = TV(np.asarray(L.g.finfo_max()))
+        y = L.where(L.cmp("eq", x, math.inf), big if posinf is None else posinf, x)
+        y = L.where(L.cmp("eq", x, -math.inf), L.un("neg", big) if neginf is None else neginf, y)
+        return L.where(_isnan(L, x), 0.0 if nan is None else nan, y)
 
     # ---- reductions --------------------------------------------------------------------------------------------
     @reg(*_ov("sum", "dim_IntList", "default"))
@@ -831,27 +872,36 @@ def _build_table():
 
     @reg(*_ov("amax", "default"))
     def _amax(L, x, dims=(), keepdim=False):
-        return L.reduce("max", x, list(dims), keepdim)
+        return L.extreme("max", x, list(dims), keepdim)
 
     @reg(*_ov("amin", "default"))
     def _amin(L, x, dims=(), keepdim=False):
-        return L.reduce("min", x, list(dims), keepdim)
+        return L.extreme("min", x, list(dims), keepdim)
 
     @reg(*_ov("max", "default"))
     def _max_all(L, x):
-        return L.reduce("max", x, None)
+        return L.extreme("max", x, None)
 
     @reg(*_ov("min", "default"))
     def _min_all(L, x):
-        return L.reduce("min", x, None)
+        return L.extreme("min", x, None)
+
+    def _first_extreme(L, x, dim, keepdim, op):
+        """max.dim / min.dim: torch's backward sends the whole gradient to the index it returns - the first extreme (or NaN)."""
+        a = np.moveaxis(L.f(x).ids, dim, -1)
+        r = a[..., -1]
+        for k in range(a.shape[-1] - 2, -1, -1):
+            xi = TV(a[..., k])
+            r = L.where(_or(L, L.cmp(op, xi, TV(r)), _isnan(L, xi)), xi, TV(r)).ids
+        return TV(np.expand_dims(r, dim % a.ndim) if keepdim else r)
 
     @reg(*_ov("max", "dim"))
     def _max_dim(L, x, dim, keepdim=False):
-        return [L.reduce("max", x, [dim], keepdim), _DataDependent("the index output of max(dim)")]
+        return [_first_extreme(L, x, dim, keepdim, "ge"), _DataDependent("the index output of max(dim)")]
 
     @reg(*_ov("min", "dim"))
     def _min_dim(L, x, dim, keepdim=False):
-        return [L.reduce("min", x, [dim], keepdim), _DataDependent("the index output of min(dim)")]
+        return [_first_extreme(L, x, dim, keepdim, "le"), _DataDependent("the index output of min(dim)")]
 
     @reg(*_ov("logsumexp", "default"))
     def _logsumexp(L, x, dims, keepdim=False):
@@ -884,8 +934,8 @@ def _build_table():
             d = L.bi("sub", x, m)
             s = L.reduce("add", L.bi("mul", d, d), dims, keepdim)
             n = int(np.prod(x.shape, dtype=np.int64)) // max(1, int(np.prod(s.shape, dtype=np.int64)))
-            v = L.bi("div", s, float(max(n - correction, 0)) if n - correction > 0 else float("nan"))
-            return L.un("sqrt", v) if std else v
+            v = L.bi("div", s, float(max(n - correction, 0)))          # torch: / max(0, n - correction) (inf or NaN past n)
+            return _safe_sqrt(L, v) if std else v
         return fn
     for o in _ov("var", "correction", "dim", "default"):
         T[o] = _var_impl(False)
@@ -899,16 +949,29 @@ def _build_table():
             a[..., k] = L._map2(lambda p, q: L.g.add(int(p), int(q)), a[..., k - 1], a[..., k])
         return TV(np.moveaxis(a, -1, dim))
 
+    def _safe_sqrt(L, s):
+        """sqrt with torch's zero gradient at 0 (std, norm): the square root of a "safe operand" - 1 where s == 0 - so that no
+        0 * inf reaches the reverse pass.  NaN / inf pass."""
+        z = L.cmp("eq", s, 0.0)
+        return L.where(z, 0.0, L.un("sqrt", L.where(z, 1.0, s)))
+
     @reg(*_ov("linalg_vector_norm", "default"), *_ov("norm", "Scalar", "ScalarOpt_dim"))
     def _norm(L, x, ord=2, dim=None, keepdim=False, dtype=None):
         ord = 2 if ord is None else ord
+        if isinstance(ord, bool) or not isinstance(ord, (int, float)) or ord == 0 or ord != ord:
+            raise Unsupported("vector norm of order %r" % (ord,))
         if ord == 2:
-            return L.un("sqrt", L.reduce("add", L.bi("mul", x, x), dim, keepdim))
+            return _safe_sqrt(L, L.reduce("add", L.bi("mul", x, x), dim, keepdim))
         if ord == 1:
             return L.reduce("add", L.un("abs", x), dim, keepdim)
-        if ord == float("inf"):
-            return L.reduce("max", L.un("abs", x), dim, keepdim)
-        return L.bi("pow", L.reduce("add", L.bi("pow", L.un("abs", x), float(ord)), dim, keepdim), 1.0 / float(ord))
+        if ord == math.inf:
+            return L.extreme("max", L.un("abs", x), dim, keepdim)
+        if ord == -math.inf:
+            return L.extreme("min", L.un("abs", x), dim, keepdim)
+        # general p: the gradient is masked at a zero norm (as torch's), through a safe operand of the outer power
+        s = L.reduce("add", L.bi("pow", L.un("abs", x), float(ord)), dim, keepdim)
+        z = L.cmp("eq", s, 0.0)
+        return L.where(z, 0.0, L.bi("pow", L.where(z, 1.0, s), 1.0 / float(ord)))
 
     @reg(*_ov("trace", "default"))
     def _trace(L, x):
