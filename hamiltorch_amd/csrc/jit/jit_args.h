@@ -1,16 +1,23 @@
 /* Kernel-argument blocks of the run-time compiled callback kernels: ONE definition, seen by the library (csrc/jit_runtime.cpp
- * fills them) and by the hipRTC translation unit (csrc/jit/hmc_callback.hip.in reads them).  Plain C, fixed-width fields,
+ * fills them) and by the hipRTC translation unit (csrc/jit/hmc_callback.hip.in and its siblings read them).  Plain C, fixed-width fields,
  * no padding surprises: pointers first, then 8-byte scalars, then 4-byte ones. */
 #ifndef HTA_JIT_ARGS_H
 #define HTA_JIT_ARGS_H
 
-#define HTA_CB_INFO_WORDS 8 /* hta_cb_info[]: {magic, D, sizeof(T), mass kind, kernel set, n_nodes, 0, 0} */
+#define HTA_CB_INFO_WORDS 8 /* hta_cb_info[]: {magic, D, sizeof(T), mass kind, kernel set, n_nodes, n_nodes3 (RMHMC) | M (split), 0} */
 #define HTA_CB_MAGIC 0x48544131 /* "HTA1" */
 
 /* kernel sets (hta_cb_info[4]): which entry points the module exports */
 #define HTA_CB_SET_HMC 1    /* hta_cb_hmc_kernel                                            */
 #define HTA_CB_SET_DERIVS 2 /* hta_cb_derivs_kernel + hta_cb_contract_kernel (Riemannian)   */
 #define HTA_CB_SET_RMHMC 3  /* hta_cb_rmhmc_kernel: explicit RMHMC trajectories, D <= 16     */
+#define HTA_CB_SET_SPLIT 4  /* hta_cb_split_kernel: split HMC on a LIST of callables          */
+
+#define HTA_CB_MAX_SPLIT 16 /* subsets of a compiled list (a subset order packs into 64 bits) */
+/* HtaCbHmcArgs::split_kind = HTA_SPLIT_SYMMETRIC / _RAND / _KMID of include/hamiltorch_amd.h */
+#define HTA_CB_SPLIT_SYMMETRIC 0
+#define HTA_CB_SPLIT_RAND 1
+#define HTA_CB_SPLIT_KMID 2
 
 typedef struct HtaCbHmcArgs {
   void* cur;               /* [C, D] current state, in / out                                                    */
@@ -22,14 +29,14 @@ typedef struct HtaCbHmcArgs {
   void* H_old;             /* [C] of the launch's LAST trajectory, or NULL                                      */
   void* H_new;             /* [C] ditto                                                                         */
   unsigned char* accept;   /* [C] ditto                                                                         */
-  void* gcur;              /* [C, D] workspace: gradient at the current state                                   */
+  void* gcur;              /* [C, D] workspace: gradient at the current state (NULL for hta_cb_split_kernel)    */
   void* lp_out;            /* [C] log p at the state the launch ended in (checked against the callback), or NULL */
   long long C;
   double eps;
   unsigned long long seed, chain_offset;
   int L, n_traj, traj_offset, burn;
   int resume;              /* 1: (log p, gradient) at `cur` are in the workspace from the previous launch of this run */
-  int reserved;
+  int split_kind;          /* hta_cb_split_kernel: HTA_CB_SPLIT_*; 0 elsewhere                                                */
   void* pre;               /* NULL, or [n_traj, D + 1, C] pre-drawn records of this launch (momentum after the mass factor, log u):
                               filled by hta_cb_predraw_kernel in front of the trajectory kernel (hta_jit_hmc_predraw_bytes)       */
   long long pre_bytes;

@@ -3,7 +3,7 @@
 // hamiltorch_amd/jit/ traces a user log_prob_func (the callback contract of hamiltorch/samplers.py:272-274), writes its
 // value / derivatives as straight-line device code and hands the SOURCE here; the hand-written kernels it is compiled into
 // live under csrc/jit/ (hmc_callback.hip.in: the reference's sample() loop for plain HMC, samplers.py:965-1026, around that
-// function; derivs_callback.hip.in: the derivatives the Riemannian samplers ask torch.func for, samplers.py:108, :397-398).
+// function; split_callback.hip.in: the same loop around a LIST of them under the split integrators, samplers.py:494-596; derivs_callback.hip.in: the derivatives the Riemannian samplers ask torch.func for, samplers.py:108, :397-398).
 //
 // Boundary rules as everywhere else: device pointers are the caller's, launches are enqueued on the caller's stream, nothing is
 // synchronised on the launch path.  Compiling (hta_jit_compile) is host work and returns a malloc'ed code object; loading
@@ -65,7 +65,7 @@ thread_local std::string g_jit_log;
 
 struct Module {
   hipModule_t mod = nullptr;
-  hipFunction_t hmc = nullptr, predraw = nullptr, derivs = nullptr, contract = nullptr, rmhmc = nullptr;
+  hipFunction_t hmc = nullptr, predraw = nullptr, derivs = nullptr, contract = nullptr, rmhmc = nullptr, split = nullptr;
   int info[HTA_CB_INFO_WORDS] = {};
   int device = -1;
 };
@@ -188,6 +188,8 @@ int hta_jit_load(const void* code, int64_t bytes, void** module_out) {
     if (e == hipSuccess) e = hipModuleGetFunction(&m->contract, m->mod, "hta_cb_contract_kernel");
   } else if (m->info[4] == HTA_CB_SET_RMHMC) {
     e = hipModuleGetFunction(&m->rmhmc, m->mod, "hta_cb_rmhmc_kernel");
+  } else if (m->info[4] == HTA_CB_SET_SPLIT) {
+    e = hipModuleGetFunction(&m->split, m->mod, "hta_cb_split_kernel");
   } else {
     e = hipErrorInvalidValue;
   }
@@ -243,6 +245,7 @@ int hta_jit_hmc_sample(void* module, const HtaCbHmcArgs* args, int D, int itemsi
   if (args->n_traj == 0) return HTA_OK;
   HtaCbHmcArgs a = *args;
   a.resume = args->resume ? 1 : 0;
+  a.split_kind = 0;
   a.gcur = workspace;
   a.lp_out = (char*)workspace + args->C * D * itemsize;
   note_route("hta_cb_hmc_kernel<D=%d,%s,mass=%d,nodes=%d%s>", D, itemsize == 4 ? "f32" : "f64", mass_kind, m->info[5],
@@ -251,6 +254,44 @@ int hta_jit_hmc_sample(void* module, const HtaCbHmcArgs* args, int D, int itemsi
   int rc = HTA_OK;
   if (a.pre) rc = launch(m->predraw, "hta_jit_hmc_sample (pre-draw)", a.C * (int64_t)a.n_traj, &a, sizeof(a), (hipStream_t)stream, 256);
   if (rc == HTA_OK) rc = launch(m->hmc, "hta_jit_hmc_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
+  profile_end((hipStream_t)stream);
+  return rc;
+}
+
+int64_t hta_jit_split_workspace_bytes(int64_t C, int D, int itemsize) {
+  if (C <= 0 || D <= 0 || (itemsize != 4 && itemsize != 8)) return -1;
+  return C * itemsize;                          // lp_out[C]: the split integrators carry log p only (their first kick is one subset's)
+}
+
+int hta_jit_split_sample(void* module, const HtaCbHmcArgs* args, int D, int M, int itemsize, int mass_kind, int split_kind,
+                         void* workspace, int64_t workspace_bytes, void* stream) {
+  using namespace hta;
+  Module* m = (Module*)module;
+  if (int rc = check_module(m, "hta_jit_split_sample", D, itemsize, mass_kind, HTA_CB_SET_SPLIT)) return rc;
+  HTA_REQUIRE(m->info[6] == M && M >= 1 && M <= HTA_CB_MAX_SPLIT, "hta_jit_split_sample: the module was compiled for %d subsets, the call has %d",
+              m->info[6], M);
+  HTA_REQUIRE(split_kind == HTA_CB_SPLIT_SYMMETRIC || split_kind == HTA_CB_SPLIT_RAND || split_kind == HTA_CB_SPLIT_KMID,
+              "hta_jit_split_sample: split kind %d", split_kind);
+  HTA_REQUIRE(M >= 2 || split_kind == HTA_CB_SPLIT_RAND, "hta_jit_split_sample: the symmetric schemes need more than one subset (S:497-498)");
+  HTA_REQUIRE(args && args->cur && args->init && args->reject_count && args->C > 0 && args->L >= 0 && args->n_traj >= 0,
+              "hta_jit_split_sample: bad arguments");
+  HTA_REQUIRE(mass_kind == HTA_MASS_NONE || (args->inv_mass && args->mass_factor), "hta_jit_split_sample: mass operands are NULL");
+  HTA_REQUIRE(!args->pre, "hta_jit_split_sample: pre-drawn records are not part of the split kernel");
+  HTA_REQUIRE(workspace && workspace_bytes >= hta_jit_split_workspace_bytes(args->C, D, itemsize),
+              "hta_jit_split_sample: workspace of %lld bytes, %lld needed (hta_jit_split_workspace_bytes)", (long long)workspace_bytes,
+              (long long)hta_jit_split_workspace_bytes(args->C, D, itemsize));
+  if (args->n_traj == 0) return HTA_OK;
+  HtaCbHmcArgs a = *args;
+  a.resume = args->resume ? 1 : 0;
+  a.split_kind = split_kind;
+  a.gcur = nullptr;
+  a.pre = nullptr;
+  a.pre_bytes = 0;
+  a.lp_out = workspace;
+  note_route("hta_cb_split_kernel<D=%d,M=%d,%s,mass=%d,kind=%s,nodes=%d>", D, M, itemsize == 4 ? "f32" : "f64", mass_kind,
+             split_kind == HTA_CB_SPLIT_RAND ? "rand" : split_kind == HTA_CB_SPLIT_KMID ? "kmid" : "symmetric", m->info[5]);
+  profile_begin((hipStream_t)stream);
+  const int rc = launch(m->split, "hta_jit_split_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
   profile_end((hipStream_t)stream);
   return rc;
 }

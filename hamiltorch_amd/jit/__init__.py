@@ -10,7 +10,8 @@ GPU ~38 eager launches per step around kernels that take microseconds.  This pac
               HIP device code;
   runtime.py  hipRTC (through the C ABI: ``hta_jit_compile`` / ``hta_jit_load``) builds that text INTO the hand-written
               kernels of ``csrc/jit/`` - for plain HMC the whole ``sample()`` loop, one chain per lane, one launch per block
-              of trajectories.
+              of trajectories; for the split integrators (``log_prob_func`` is a LIST of callables, one per data subset) the
+              same loop around all of them: ``compile_split``, ``csrc/jit/split_callback.hip.in``.
 
 No inductor, no Triton, no code from torch's compiler stack beyond the tracer.  A callable the tracer or the lowering table
 does not cover (data-dependent control flow, the tuple / ``pass_grad`` protocols, unlisted operations, graphs that are too
@@ -155,6 +156,81 @@ def _compile(fn, example, dtype, mass_kind, fresh):
         try:
             with _lock:
                 _by_fn.setdefault(fn, {})[cfg] = (sig, objs, out)
+        except TypeError:
+            pass
+    if isinstance(out, Unsupported):
+        raise out
+    return out
+
+
+class CompiledSplit(CompiledHMC):
+    """A LIST of traced callables (one per data subset) compiled into the split-HMC trajectory kernel
+    (csrc/jit/split_callback.hip.in) for one (D, dtype, mass kind); `traced` is the list of traces, `M` its length."""
+
+    @property
+    def M(self):
+        return len(self.traced)
+
+
+def compile_split(fns, example, dtype, mass_kind, fresh=False):
+    """CompiledSplit for the list of callables ``fns`` (Integrator.SPLITTING / SPLITTING_RAND / SPLITTING_KMID: one callable per
+    data subset) at points shaped like the (D,) tensor ``example``; raises ``Unsupported``.  Every callable is traced and checked
+    against torch.autograd like a single one; one unsupported subset makes the whole list unsupported, and the reason names it.
+    The result is reused while the tuple of the callables' closure signatures is unchanged (``fresh=True`` traces again)."""
+    _note("")
+    fns = list(fns)
+    mass_kind = int(mass_kind)
+    cfg = ("split", len(fns), int(example.numel()), dtype, mass_kind, example.device.type)
+    sig = objs = refs = None
+    ent = None
+    try:
+        if not fns or not all(callable(f) for f in fns):
+            raise TypeError
+        parts = [_signature(f) for f in fns]
+        sig, objs = tuple(p[0] for p in parts), [p[1] for p in parts]
+        refs = [weakref.ref(f) for f in fns[1:]]
+        with _lock:
+            ent = _by_fn.get(fns[0], {}).get(cfg)
+    except TypeError:       # an empty list, or a member that is not weak-referenceable / hashable: no reuse
+        ent = None
+        sig = None
+    if ent is not None and not fresh and ent[0] == sig and len(ent[3]) == len(fns) - 1 and all(r() is f for r, f in zip(ent[3], fns[1:])):
+        stats["trace_hits"] += 1
+        if isinstance(ent[2], Unsupported):
+            _note(str(ent[2]))
+            raise ent[2]
+        return ent[2]
+    try:
+        if not fns:
+            raise Unsupported("an empty list of callables")
+        if len(fns) > runtime.MAX_SPLIT:
+            raise Unsupported("%d subsets: the split kernel builds in at most %d callables" % (len(fns), runtime.MAX_SPLIT))
+        traced = []
+        for m, fn in enumerate(fns):
+            try:
+                if not callable(fn):
+                    raise Unsupported("not a callable")
+                tr = trace_callback(fn, example)
+                stats["traced"] += 1
+                _check_against_autograd(tr, fn, example)
+            except Unsupported as e:
+                raise Unsupported("subset %d: %s" % (m, e)) from None
+            traced.append(tr)
+        key, blob = runtime.compile_source(runtime.split_generated_source(traced, dtype, mass_kind), runtime.SKELETON_SPLIT)
+        out = CompiledSplit(traced, key, blob, dtype, mass_kind)
+    except Unsupported as e:
+        stats["unsupported"] += 1
+        _note(str(e))
+        out = e
+    except runtime.CompileError as e:
+        stats["unsupported"] += 1
+        first = next((ln for ln in e.log.splitlines() if "error" in ln), str(e).splitlines()[0])
+        out = Unsupported("hipRTC rejected the generated code: %s" % first.strip()[:160])
+        _note(str(out))
+    if sig is not None:
+        try:
+            with _lock:
+                _by_fn.setdefault(fns[0], {})[cfg] = (sig, objs, out, refs)
         except TypeError:
             pass
     if isinstance(out, Unsupported):

@@ -19,8 +19,9 @@ from .ir import Unsupported
 
 _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 _HEADERS = (("cb_math.hpp", "jit/cb_math.hpp"), ("philox.hpp", "philox.hpp"), ("mh_rules.hpp", "mh_rules.hpp"),
-            ("jit_args.h", "jit/jit_args.h"))
+            ("jit_args.h", "jit/jit_args.h"), ("cb_hmc_shared.hpp", "jit/cb_hmc_shared.hpp"))
 SKELETON_HMC = "jit/hmc_callback.hip.in"
+SKELETON_SPLIT = "jit/split_callback.hip.in"
 SKELETON_DERIVS = "jit/derivs_callback.hip.in"
 SKELETON_RMHMC = "jit/rmhmc_callback.hip.in"
 # (SLP vectorisation ON: the straight-line callback code packs into v_pk_mul / v_pk_fma pairs - 67 -> 59 instructions per
@@ -189,6 +190,63 @@ def hmc_final_logp(workspace, C, D, dtype):
     """log p at the state the last launch ended in ([C] view of the workspace's second block)."""
     item = torch.empty((), dtype=dtype).element_size()
     return workspace[C * D * item:C * D * item + C * item].view(dtype)
+
+
+# ---- split HMC on a list of callables ---------------------------------------------------------------------------------
+MAX_SPLIT = 16                  # subsets of one compiled list (HTA_CB_MAX_SPLIT: a subset order packs into 64 bits)
+MAX_SPLIT_NODES = MAX_HMC_NODES  # SUM of the subsets' live value + gradient operations (DESIGN.md 4a)
+
+
+def split_generated_source(traced_list, dtype, mass_kind):
+    """The generated include of csrc/jit/split_callback.hip.in for a list of traced callables (one per data subset)."""
+    M = len(traced_list)
+    if M < 1:
+        raise Unsupported("an empty list of callables")
+    if M > MAX_SPLIT:
+        raise Unsupported("%d subsets: the split kernel builds in at most %d callables" % (M, MAX_SPLIT))
+    dims = [t.D for t in traced_list]
+    if len(set(dims)) != 1:
+        raise Unsupported("the subsets do not share one parameter vector (D = %s)" % ", ".join(str(d) for d in dims))
+    D = dims[0]
+    if D > MAX_HMC_DIM:
+        raise Unsupported("D = %d: the chain-per-lane kernel holds theta, p and the gradient in registers (D <= %d)" % (D, MAX_HMC_DIM))
+    live = [len(t.graph.reachable([t.value] + t.grad())) for t in traced_list]
+    if sum(live) > MAX_SPLIT_NODES:
+        raise Unsupported("value + gradient of the %d subsets are %d scalar operations in all (limit %d)" % (M, sum(live), MAX_SPLIT_NODES))
+    return emit.split_value_grad_source(traced_list, dtype_name(dtype), mass_kind)
+
+
+def split_workspace_bytes(C, D, itemsize):
+    return int(_abi.load().hta_jit_split_workspace_bytes(int(C), int(D), int(itemsize)))
+
+
+def split_sample(module, cur, init, M, split_kind, mass_kind, inv_mass, mass_factor, L, eps, n_traj, traj_offset, burn, seed,
+                 chain_offset, samples, reject_count, workspace, H_old=None, H_new=None, accept=None, resume=False):
+    """hta_jit_split_sample: trajectories [traj_offset, traj_offset + n_traj) of a split integrator on the compiled list, one launch."""
+    _abi.require_device(cur, "params")
+    C, D = cur.shape
+    a = _abi.HtaCbHmcArgs()
+    a.cur, a.init = cur.data_ptr(), _abi._p(init, cur).value
+    a.inv_mass = None if inv_mass is None else _abi._p(inv_mass, cur).value
+    a.mass_factor = None if mass_factor is None else _abi._p(mass_factor, cur).value
+    a.samples = None if samples is None else _abi._p(samples, cur).value
+    a.reject_count = reject_count.data_ptr()
+    a.H_old = None if H_old is None else _abi._p(H_old, cur).value
+    a.H_new = None if H_new is None else _abi._p(H_new, cur).value
+    a.accept = None if accept is None else accept.data_ptr()
+    a.C, a.eps, a.seed, a.chain_offset = C, float(eps), int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_offset)
+    a.L, a.n_traj, a.traj_offset, a.burn = int(L), int(n_traj), int(traj_offset), int(burn)
+    a.resume, a.split_kind = (1 if resume else 0), int(split_kind)
+    with torch.cuda.device(cur.device):
+        _abi._check(_abi.load().hta_jit_split_sample(module.handle, ctypes.byref(a), D, int(M), cur.element_size(), int(mass_kind),
+                                                     int(split_kind), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                                     _abi._stream(cur)), "hta_jit_split_sample")
+
+
+def split_final_logp(workspace, C, dtype):
+    """Sum of the subsets' log p at the state the last launch ended in ([C] view of the workspace)."""
+    item = torch.empty((), dtype=dtype).element_size()
+    return workspace[:C * item].view(dtype)
 
 
 # ---- derivatives for the Riemannian samplers ---------------------------------------------------------------------------

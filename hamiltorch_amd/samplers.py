@@ -423,7 +423,7 @@ def sample(log_prob_func, params_init, num_samples=10, num_steps_per_sample=10, 
                 if isinstance(inv_mass, list):
                     raise NotImplementedError("block-list inv_mass performs no drift in the reference's split "
                                               "integrator (S:514-515); not supported")
-                eng = _resolve_split_engine(log_prob_func, theta0, native, integrator)
+                eng = _resolve_split_engine(log_prob_func, theta0, native, integrator, inv_mass)
             else:
                 tgt = as_gaussian(log_prob_func, theta0) if (native and pass_grad is None) else None
                 if tgt is None and native and pass_grad is None:
@@ -463,6 +463,16 @@ def sample(log_prob_func, params_init, num_samples=10, num_steps_per_sample=10, 
                                   "states; re-running on the torch-evaluated callback path" % (log_prob_func,))
                     _abi.load().hta_jit_note_fallback(b"compiled code disagrees with the callable")
                     (samples, rejected), step_size_out = run(_GenericHMC(log_prob_func, pass_grad))
+            if isinstance(eng, _CompiledSplitHMC) and not eng.verify():
+                # the same rule for a compiled LIST: trace again once if the trace was a reused one, else the generic split engine
+                eng2 = _compiled_split_engine(log_prob_func, theta0, inv_mass, integrator, fresh=True) if eng.reused else None
+                if eng2 is not None:
+                    (samples, rejected), step_size_out = run(eng2)
+                if eng2 is None or not eng2.verify():
+                    warnings.warn("hamiltorch_amd: the compiled form of %r disagrees with the callables themselves on the sampled "
+                                  "states; re-running on the torch-evaluated callback path" % (log_prob_func,))
+                    _abi.load().hta_jit_note_fallback(b"compiled code disagrees with the callable")
+                    (samples, rejected), step_size_out = run(_GenericHMC(log_prob_func, split=True, integrator=integrator))
             step_size = step_size_out
         elif sampler == Sampler.RMHMC and integrator == Integrator.EXPLICIT:
             if pass_grad is not None:
@@ -833,6 +843,80 @@ class _CompiledHMC(_Engine):
         return bool(((fin_a == fin_b) & (close | ~fin_b)).all())
 
 
+_SPLIT_KIND_OF = {Integrator.SPLITTING: _abi.SPLIT_SYMMETRIC, Integrator.SPLITTING_RAND: _abi.SPLIT_RAND,
+                  Integrator.SPLITTING_KMID: _abi.SPLIT_KMID}
+
+
+def _compiled_split_engine(log_prob_list, theta0, inv_mass, integrator, fresh=False):
+    """The callback compiler's engine for a LIST of callables under a split integrator, or None (the reason goes to
+    hta_last_route() / jit.last_reason())."""
+    from . import jit
+    ok = len(log_prob_list) > 0 and all(callable(f) for f in log_prob_list)
+    if not jit.enabled() or not ok:
+        _abi.load().hta_jit_note_fallback(b"HAMILTORCH_AMD_JIT=0" if ok else b"not a list of callables")
+        return None
+    if len(log_prob_list) == 1 and integrator != Integrator.SPLITTING_RAND:
+        _abi.load().hta_jit_note_fallback(b"one subset: the symmetric split schemes need more")     # (the generic engine raises S:497-498)
+        return None
+    before = jit.stats["trace_hits"]
+    try:
+        comp = jit.compile_split(log_prob_list, theta0[0], theta0.dtype, _mass_kind_of(inv_mass), fresh=fresh)
+    except jit.Unsupported as e:
+        _abi.load().hta_jit_note_fallback(str(e)[:140].encode("utf-8", "replace"))
+        return None
+    return _CompiledSplitHMC(log_prob_list, comp, _SPLIT_KIND_OF[integrator], reused=jit.stats["trace_hits"] > before)
+
+
+class _CompiledSplitHMC(_Engine):
+    """A list of opaque callables (one per data subset) compiled into the split trajectory kernel (hamiltorch_amd/jit/,
+    csrc/jit/split_callback.hip.in): a block of trajectories per launch - momentum draw, the 2 M stages of every step with the
+    subsets' gradients built in and chosen by a wave-uniform branch, energies, Metropolis, burn / Q2 bookkeeping and row stores
+    in one kernel, one chain per lane."""
+
+    def __init__(self, fns, compiled, split_kind, reused=False):
+        self.fns, self.comp, self.split_kind, self.reused = list(fns), compiled, split_kind, reused
+
+    def begin(self, theta0, N, burn, inv_mass, seed, chain_offset):
+        from .jit import runtime
+        super().begin(theta0, N, burn, inv_mass, seed, chain_offset)
+        C, D = theta0.shape
+        self.module = self.comp.module(theta0.device)
+        self.ws = torch.empty(runtime.split_workspace_bytes(C, D, theta0.element_size()), dtype=torch.uint8, device=theta0.device)
+        self._ran = False
+
+    def advance(self, n0, count, L, eps, H_old=None, H_new=None, progress=None):
+        from .jit import runtime
+        # one launch per block of trajectories (one trajectory when the energies are read back: the NUTS burn-in); a visible
+        # progress bar cuts the run into ~20 launches so that it moves
+        chunk = 1 if H_old is not None else (max(1, -(-count // 20)) if (progress is not None and progress.enabled) else count)
+        for start in range(n0, n0 + count, chunk):
+            k = min(chunk, n0 + count - start)
+            runtime.split_sample(self.module, self.cur, self.theta0, self.comp.M, self.split_kind, self.kind, self.im, self.mf, L, eps,
+                                 k, start, self.burn, self.seed, self.off, self.samples, self.rejected, self.ws, H_old, H_new,
+                                 resume=self._ran)
+            self._ran = True
+            if progress is not None:
+                progress.update(min(self.N, start + k) - 1)
+
+    def verify(self, k=128):
+        """The kernel's own log p of the states the run ended in against the SUM of the callables evaluated by torch on up to `k`
+        chains.  False = the compiled code does not compute these callables (see sample())."""
+        from . import jit
+        if not self._ran or os.environ.get("HAMILTORCH_AMD_JIT_VERIFY", "1") == "0":
+            return True
+        C, D = self.cur.shape
+        idx = slice(0, min(C, k))
+        mine = jit.runtime.split_final_logp(self.ws, C, self.cur.dtype)[idx]
+        ref = None
+        for fn in self.fns:
+            v = jit.torch_logp(fn, self.cur[idx]).to(mine.dtype).reshape(-1)
+            ref = v if ref is None else ref + v
+        fin_a, fin_b = torch.isfinite(mine), torch.isfinite(ref)
+        tol = (2e-4 if mine.dtype == torch.float32 else 1e-9)
+        close = (mine - ref).abs() <= tol * (10.0 + ref.abs())
+        return bool(((fin_a == fin_b) & (close | ~fin_b)).all())
+
+
 class _GenericHMC(_Engine):
     """Generic-callback path (plain HMC, S:267-304) -- also the SPLITTING integrator when given a
     list of callbacks (S:494-547)."""
@@ -985,9 +1069,15 @@ class _GenericHMC(_Engine):
         return graph
 
 
-def _resolve_split_engine(log_prob_list, theta0, native, integrator=Integrator.SPLITTING):
+def _resolve_split_engine(log_prob_list, theta0, native, integrator=Integrator.SPLITTING, inv_mass=None):
+    """The native MLP kernels for closures that carry `_hta_spec`, else the callback compiler (jit/: the list built into one fused
+    kernel), else the torch-evaluated generic engine."""
     from . import bnn
     eng = bnn.native_split_engine(log_prob_list, theta0, integrator) if native else None
+    if eng is None and native:
+        eng = _compiled_split_engine(log_prob_list, theta0, inv_mass, integrator)
+    elif eng is None:
+        _abi.load().hta_jit_note_fallback(b"native=False")
     return eng if eng is not None else _GenericHMC(log_prob_list, split=True, integrator=integrator)
 
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HTA_ABI_VERSION 11
+#define HTA_ABI_VERSION 12
 
 #define HTA_OK 0
 #define HTA_ERR_INVALID (-1)   /* bad argument                           */
@@ -429,11 +429,16 @@ int hta_net_forward_f64(const double* theta, int64_t S, int n_layers, const int*
  *                     messages.  HTA_ERR_UNSUPPORTED: libhiprtc.so is not loadable.
  *   hta_jit_load      code object -> module on the CURRENT device (a preparation step: reads the module's info block back
  *                     once); hta_jit_unload frees it.  hta_jit_module_info: {magic, D, sizeof(T), mass kind, kernel set,
- *                     scalar operations, 0, 0}.
+ *                     scalar operations, third-order operations (RMHMC) | M (split), 0}.
  *   hta_jit_hmc_sample  trajectories [traj_offset, traj_offset + n_traj) of plain HMC for C chains; the argument block is
  *                     HtaCbHmcArgs (csrc/jit/jit_args.h; `gcur` / `lp_out` are placed in `workspace`,
  *                     hta_jit_hmc_workspace_bytes(C, D, itemsize) bytes).  Same streams, rules and outputs as the pieces
  *                     above; D / itemsize / mass_kind must be the module's (else HTA_ERR_INVALID, nothing is launched).
+ *   hta_jit_split_sample  (ABI 12) the same for a LIST of M callables (one per data subset, S:466) under Integrator.SPLITTING /
+ *                     SPLITTING_RAND / SPLITTING_KMID (S:494-596): csrc/jit/split_callback.hip.in, the subset functions built in
+ *                     once each and dispatched by a wave-uniform branch.  HtaCbHmcArgs with `split_kind`; `pre` must be NULL;
+ *                     `lp_out` is placed in `workspace` (hta_jit_split_workspace_bytes(C, D, itemsize) bytes).  D / M /
+ *                     itemsize / mass_kind must be the module's.
  *   hta_jit_derivs    which = 0: logp[C], grad[C,D], neg_hess[C,D,D] (each optional) at theta[C,D]; which = 1:
  *                     contract[C,D] = d_k < Hess log p, M > with M[C,D,D] held fixed.
  *   hta_jit_note_fallback  records in hta_last_route() WHY a callable was not compiled (the caller then runs the pieces path).
@@ -455,6 +460,9 @@ int64_t hta_jit_hmc_workspace_bytes(int64_t C, int D, int itemsize);
 int64_t hta_jit_hmc_predraw_bytes(int64_t C, int D, int n_traj, int itemsize);
 int hta_jit_hmc_sample(void* module, const HtaCbHmcArgs* args, int D, int itemsize, int mass_kind, void* workspace,
                        int64_t workspace_bytes, void* stream);
+int64_t hta_jit_split_workspace_bytes(int64_t C, int D, int itemsize);
+int hta_jit_split_sample(void* module, const HtaCbHmcArgs* args, int D, int M, int itemsize, int mass_kind, int split_kind,
+                         void* workspace, int64_t workspace_bytes, void* stream);
 int hta_jit_derivs(void* module, const HtaCbDerivArgs* args, int which, int D, int itemsize, void* stream);
 /* Explicit RMHMC (S:389-462 inside the RMHMC branch of sample(), S:969-1026; Metric.SOFTABS) for a GENERAL target of small dimension
  * (D <= 16) on a compiled callable: trajectories [traj_offset, traj_offset + n_traj), a chain per lane, the 8 L + 3 metric evaluations
