@@ -735,7 +735,9 @@ __global__ __launch_bounds__(256) void hmc_gauss_eig_kernel(GaussArgs<T> a, cons
 #define QUAD_FUSED_NS 4
 #endif
 // Developer builds only (profiles/r05y_quad_ablation.txt: timing of the trajectory's parts, wrong samples): -DQUAD_FUSED_NS=n -DQUAD_SLOTS=m (a deeper
-// record look-ahead: measured, no effect), -DQUAD_ABLATE_STORE / _LOAD / _ACC / _TAIL (one cost of a trajectory removed at a time).
+// record look-ahead: measured, no effect), -DQUAD_ABLATE_STORE / _LOAD / _ACC / _TAIL (one cost of a trajectory removed at a time),
+// -DQUAD_ABLATE_ROWS (profiles/r07a_quad_rows.txt: the integrating wave of "quad_rows" with nobody reading its ring), -DQUAD_ROWS_NI=1|4
+// (the other placements of the row waves: correct samples).
 #ifndef QUAD_SLOTS
 #define QUAD_SLOTS 4
 #endif
@@ -783,13 +785,36 @@ template <int I, int N, typename F> __device__ __forceinline__ void quad_static_
 // path (inside the once-per-chunk poll and after the loops).  Debug key "quad_starve" makes the producers leave at once (the test
 // of this path: tests/test_gpu_hmc.py::test_fused_launch_reports_starved_producers).
 struct QuadFused { uint32_t* flags; int ch; uint32_t target; int nchunks; uint32_t* err; int starve; };
-template <int D, bool DIAG, int LB, int VAR, bool FUSED>
-__device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t gt, const QuadFused fz) {
+// ROWS (tuning key "quad_rows", default 1): the OUTPUT side of a chain - the proposal's row element q = mu + Tout y, the select of the
+// stored element, the row store, the final state, the reject count, the NaN rows of a starved launch - runs on a ROW WAVE of the
+// same workgroup (quad_rows_body below); the integrating wave keeps the chain and the accept test and hands each trajectory's
+// outcome over through LDS.
+//   message   one dword per trajectory and lane: acc ? y : 0xFFFFFFFF.  The sentinel is a NaN pattern, and an accepted y is never
+//             NaN (a NaN or infinite y makes lam y^2, hence dH, NaN or -inf, which the compare rejects; a lane with lam = 0 adds a
+//             finite eps r to a finite y), so the row wave rebuilds acc and q exactly: the same v_fmac_f32_dpp sequence on the same y.
+//   ring      per integrating wave two buffers of one pass each (NU positions x 64 lanes); the slot address is the lane's base
+//             register plus the immediate offset of the position in the unrolled pass - no address arithmetic on the hot path.
+//   cost      <3, 25>: 67.5 instructions per trajectory on the integrating wave instead of 73.3 (tests/test_quad_rows_resources.py
+//             holds it under 68); 0.148 -> 0.139 ms per 1000 trajectories at BASELINE config 2 (profiles/r07a_quad_rows.txt).
+//   hand-over one "s_waitcnt lgkmcnt(0) ; s_barrier" per GROUP of trajectories (a pass of NU, a tail pass of NS, a single one) on
+//             both roles: the integrator after it filled buffer g % 2, the row wave before it reads it.  The row wave reaches barrier
+//             g + 1 only after it has read group g, and the integrator refills buffer g % 2 only after barrier g + 1.  Both roles
+//             derive the sequence of groups from the same launch arguments (quad_groups), so every wave of the block - also one
+//             whose chains lie past a.C: it integrates the last chain again and stores nothing - reaches every barrier.
+// Results are bit-identical to "quad_rows" = 0 (tests/test_gpu_quad_rows.py).
+constexpr int quad_fused_ns(int LB, bool FUSED) { return FUSED ? QUAD_FUSED_NS : (LB == 5 ? 4 : (LB == 10 ? 3 : 2)); }
+constexpr int quad_nu(int LB, int NS, bool UADDR) { return UADDR ? (LB == 25 ? (NS > 4 ? 4 : 8) : 4) * NS : 2 * NS; }
+constexpr uint32_t QUAD_ROWS_REJECT = 0xFFFFFFFFu;
+template <int D, bool DIAG, int LB, int VAR, bool FUSED, bool ROWS = false>
+__device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t gt, const QuadFused fz,
+                                          uint32_t lds = 0) {
   typedef float T;
   constexpr bool UADDR = (VAR & 1) != 0, NOGUARD = (VAR & 2) != 0, TAIL = (VAR & 4) != 0;
-  const int64_t c = gt >> 2;
+  static_assert(!ROWS || (FUSED && UADDR && TAIL && !DIAG), "the row-wave form is an instance of the fused launch");
+  const bool on = (gt >> 2) < a.C;
+  const int64_t c = ROWS ? (on ? gt >> 2 : a.C - 1) : gt >> 2;       // ROWS: every wave stays for the barriers
   const int k = (int)(gt & 3);
-  if (c >= a.C) return;                         // whole quads leave together
+  if constexpr (!ROWS) { if (c >= a.C) return; }                     // whole quads leave together
   // FUSED: rows [0, ready) are known complete; the counter of the chunk that starts at row `ready` was requested when the previous
   // chunk was confirmed (pf).  The hot path pays one compare per pass; the poll runs once per chunk, out of the straight line.
   int ready = 0;
@@ -859,7 +884,7 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   T yc = to_y(a.theta);
   // the row element this lane stores: kept as it was written (a rejected trajectory repeats the previous row bit for bit,
   // the first rows repeat params_init exactly, S:1018) - only an accepted proposal is mapped back, q = mu + Tout y
-  T qc = a.theta[c * D + kk];
+  T qc = ROWS ? 0.f : a.theta[c * D + kk];        // (ROWS: the row wave's)
   // Energies are carried DOUBLED (2 x potential share = lam y^2, 2 x kinetic share = r^2; the record holds 2 log u): one
   // multiply less per energy, and scaling by two commutes with rounding, so the decisions are those of the plain form.
   T potc = lam * yc * yc;                        // twice this coordinate's share of the potential at the current point
@@ -874,7 +899,7 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   const size_t rec_step = C * W;
   // Records are read NS trajectories ahead: a trajectory (~90 ns at L = 5, ~180 ns at L = 25) is shorter than the ~250 ns
   // an HBM load takes to return, and the look-ahead has to cover it.  The workspace carries QUAD_SLOTS_MAX rows of slack.
-  constexpr int NS = FUSED ? QUAD_FUSED_NS : (LB == 5 ? 4 : (LB == 10 ? 3 : 2));     // (FUSED: the records come from memory, not from this XCD's L2)
+  constexpr int NS = quad_fused_ns(LB, FUSED);     // (FUSED: the records come from memory, not from this XCD's L2)
   static_assert(NS <= QUAD_SLOTS_MAX, "workspace slack");
   T zs[NS], lus[NS];
   need_rows(NS - 1);
@@ -888,11 +913,26 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   const uint32_t qoff = (uint32_t)(((size_t)c * D + kk) * sizeof(T));
   typedef __attribute__((address_space(1))) char* gwbytes_t;
   auto put = [&](gwbytes_t row, T v) { *(__attribute__((address_space(1))) T*)(row + qoff) = v; };
-  put((gwbytes_t)a.theta, to_q(yc));
+  if constexpr (!ROWS) put((gwbytes_t)a.theta, to_q(yc));
   // UADDR: the record of the trajectory at position i of the unrolled loop is recb + roff[i] (recb: the row NS ahead of the
   // pass's first trajectory), its stored row element rowb + soff[i]; both bases are wave-uniform and move once per pass.
   // (the dispatcher bounds C so that the offsets stay below 2^32)
-  constexpr int NU = UADDR ? (LB == 25 ? (NS > 4 ? 4 : 8) : 4) * NS : 2 * NS;       // trajectories per pass of the unrolled loop (the scalar bookkeeping of a pass is shared)
+  constexpr int NU = quad_nu(LB, NS, UADDR);       // trajectories per pass of the unrolled loop (the scalar bookkeeping of a pass is shared)
+  // ROWS: the message of the trajectory at position i of a group goes to lds + 256 i (64 lanes x 4 bytes); `lds` flips between the two buffers
+  const uint32_t lds_both = 2u * lds + (uint32_t)(NU * 256);
+  T pend_y = 0.f;                                // the last trajectory's proposal and decision: its message is still to be written (D < 4)
+  uint64_t pend_mask = 0;
+  auto handover = [&](auto G) {                  // after a group of G trajectories
+    if constexpr (ROWS) {
+      if constexpr (D < 4) {
+        T msg;
+        asm volatile("v_cndmask_b32_e64 %0, -1, %1, %2\n\tds_write_b32 %3, %0 offset:%4"
+                     : "=&v"(msg) : "v"(pend_y), "s"(pend_mask), "v"(lds), "n"((decltype(G)::value - 1) * 256));
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      lds = lds_both - lds;
+    }
+  };
   typedef const __attribute__((address_space(1))) char* gcbytes_t;
   gcbytes_t recb = (gcbytes_t)a.ws_z + (size_t)NS * (rec_step * sizeof(T));
   uint32_t roff[NU], uoff[NU], soff[NU];
@@ -929,6 +969,8 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
       T y = yc, r, eo, logu;
       {
         const T z = slot;
+        if constexpr (ROWS && D < 4) logu = 0.f;      // (broadcast inside the butterfly block below: one of its wait states)
+        else
         logu = D == 4 ? slot_u
                       : __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, z), (D < 4 ? D : 0) * 0x55,
                                                                             0xF, 0xF, true));
@@ -937,7 +979,8 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
       }
       // (the empty asm orders the refill after the record's last use, so the load can target the record's own register;
       //  otherwise the scheduler hoists the load and the back-edge copy of its result waits for it)
-      if constexpr (UADDR) {
+      if constexpr (ROWS && D < 4) {
+      } else if constexpr (UADDR) {
         asm volatile("" : "+v"(roff[pos]) : "v"(r), "v"(eo), "v"(logu));
 #if defined(QUAD_ABLATE_LOAD4)      // timing only (needs -DQUAD_FUSED_NS=8 -DQUAD_SLOTS=8): ONE 16-byte load per four trajectories into the four slots just consumed
         if constexpr (decltype(pos)::value % 4 == 3 && NS == 8) {
@@ -979,7 +1022,36 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
 #define HTA_B1 "\n\tv_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
 #define HTA_B2 "\n\tv_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1"
         dH = eo - en;
-        if constexpr (D == 1)
+        if constexpr (ROWS && D < 4) {
+          // The row element is the row wave's.  The two wait states in front of each stage of the butterfly are useful instructions:
+          //   d = eo - en (compiler) | select of the PREVIOUS trajectory's message | log u broadcast | d += d[lane^1] | LDS write of that
+          //   message | record refill (compiler; volatile asm on both sides keeps it there) | d += d[lane^2]
+          // - the message of a trajectory is selected and written one trajectory late (the last one of a group: flush, before the
+          // hand-over), so the integrating wave spends no s_nop on the butterfly; the first trajectory of a group has no message to
+          // carry and pads with two.
+          qp = 0.f;
+          constexpr int P = decltype(pos)::value;
+          if constexpr (P > 0) {
+            T msg;
+            asm volatile("v_cndmask_b32_e64 %2, -1, %4, %5\n\tv_mov_b32_dpp %1, %3 quad_perm:[%8,%8,%8,%8] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                         "\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                         "\n\tds_write_b32 %6, %2 offset:%7"
+                         : "+v"(dH), "=&v"(logu), "=&v"(msg)
+                         : "v"(slot), "v"(pend_y), "s"(pend_mask), "v"(lds), "n"((P - 1) * 256), "n"(D));
+          } else {
+            asm volatile("v_mov_b32_dpp %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\ts_nop 0" "\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1" "\n\ts_nop 0"
+                         : "+v"(dH), "=&v"(logu) : "v"(slot), "n"(D));
+          }
+          asm volatile("" : "+v"(roff[pos]));            // keeps the zero-extension next to its use: base + 32-bit offset addressing
+          slot = *(grec_t)(recb + roff[pos]);
+          // second stage, the compare and the selects of yc and potc in one block (the compiler pads a wait state between two blocks)
+          asm volatile("v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_cmp_ge_f32_e64 %3, %0, %4\n\t"
+                       "v_cndmask_b32_e64 %1, %1, %5, %3\n\tv_cndmask_b32_e64 %2, %2, %6, %3"
+                       : "+v"(dH), "+v"(yc), "+v"(potc), "=&s"(pend_mask) : "v"(logu), "v"(y), "v"(pot1));
+          pend_y = y;                                    // its message: inside the next trajectory's block, or by the hand-over
+        }
+        else if constexpr (ROWS) { qp = 0.f; dH = quad_sum(dH); }      // (D = 4: log u is a second record element; the compiler pads the DPP wait states)
+        else if constexpr (D == 1)
           asm volatile("v_mov_b32 %0, %3" HTA_QG(0, 4) HTA_B1 "\n\ts_nop 1" HTA_B2
                        : "=&v"(qp), "+v"(dH) : "v"(y), "v"(mu), "v"(Qrow[0]));
         else if constexpr (D == 2)
@@ -1020,9 +1092,22 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
 #if defined(QUAD_ABLATE_ACC)
       const uint64_t accmask = ~0ull; asm volatile("" :: "v"(dH), "v"(logu));
 #else
-      const uint64_t accmask = __builtin_amdgcn_fcmpf(NOGUARD ? dH : __builtin_fmaf(dH, 0.0f, dH), logu, 3 /* oge */);
+      const uint64_t accmask = (ROWS && D < 4) ? pend_mask : __builtin_amdgcn_fcmpf(NOGUARD ? dH : __builtin_fmaf(dH, 0.0f, dH), logu, 3 /* oge */);
 #endif
-      if constexpr (!decltype(q2)::value) {
+      if constexpr (ROWS) {
+        // yc, potc <- accepted point; the message acc ? y : sentinel (-1 is an inline constant) into this position's slot of the ring.
+        // The accepted count is the row wave's as well.  (D < 4: all of it happened in the butterfly blocks above.)
+        if constexpr (D == 4) {
+          T msg;
+          asm volatile("v_cndmask_b32_e64 %0, %0, %3, %5\n\tv_cndmask_b32_e64 %1, %1, %4, %5\n\tv_cndmask_b32_e64 %2, -1, %3, %5\n\t"
+                       "ds_write_b32 %6, %2 offset:%7"
+                       : "+v"(yc), "+v"(potc), "=&v"(msg)
+                       : "v"(y), "v"(pot1), "s"(accmask), "v"(lds), "n"(decltype(pos)::value * 256));
+        }
+        if constexpr (decltype(q2)::value) {
+          if (!((accmask >> (threadIdx.x & 63)) & 1)) { yc = to_y(a.theta_init); potc = lam * yc * yc; }      // Q2: back to params_init itself
+        }
+      } else if constexpr (!decltype(q2)::value) {
         // accepted += acc; yc, potc, qc <- accepted point: a carry-in add and three selects on the accept mask
         uint64_t carry_out;
         asm volatile("v_addc_co_u32_e64 %0, %4, 0, %0, %5\n\tv_cndmask_b32_e64 %1, %1, %6, %5\n\tv_cndmask_b32_e64 %2, %2, %7, %5\n\t"
@@ -1039,7 +1124,8 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
           yc = to_y(a.theta_init); potc = lam * yc * yc; qc = a.theta_init[c * D + kk];
         }
       }
-      if constexpr (UADDR) {
+      if constexpr (ROWS) {
+      } else if constexpr (UADDR) {
         asm volatile("" : "+v"(soff[pos]));            // keeps the zero-extension next to its use: base + 32-bit offset addressing
 #if !defined(QUAD_ABLATE_STORE)
         *(__attribute__((address_space(1))) T*)(row + soff[pos]) = qc;
@@ -1076,18 +1162,21 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
         trajectory(zs[0], lus[0], std::true_type{}, first);
         moved(1);
         rotate();
+        handover(std::integral_constant<int, 1>{});
       }
       while (t + NU - 1 < t_end) {
         need_rows(t + NU - 1 + NS);
         quad_static_for<0, NU>([&](auto I) { trajectory(zs[I % NS], lus[I % NS], plain, I); });
         moved(NU);
+        handover(std::integral_constant<int, NU>{});
       }
       while (t + NS - 1 < t_end) {
         need_rows(t + NS - 1 + NS);
         quad_static_for<0, NS>([&](auto I) { trajectory(zs[I], lus[I], plain, I); });
         moved(NS);
+        handover(std::integral_constant<int, NS>{});
       }
-      while (t < t_end) { need_rows(t + NS); trajectory(zs[0], lus[0], plain, first); moved(1); rotate(); }
+      while (t < t_end) { need_rows(t + NS); trajectory(zs[0], lus[0], plain, first); moved(1); rotate(); handover(std::integral_constant<int, 1>{}); }
     } else {
       if (phase == 1 && t < t_end && a.traj_offset + t == a.burn + 1) {              // the Q2 trajectory opens the stored phase
         trajectory(zs[0], lus[0], std::true_type{}, first);
@@ -1104,6 +1193,10 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
       while (t < t_end) { trajectory(zs[0], lus[0], plain, first); rotate(); }
     }
   }
+  if constexpr (ROWS) {                           // one more group: whether this wave's hand-over from the producers failed
+    asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" :: "v"(lds), "v"(starved ? 1u : 0u) : "memory");
+    return;
+  }
   if constexpr (FUSED) {
     if (__builtin_expect(starved, 0)) {           // see QuadFused: the rows of this launch and the chain state become NaN
       qc = __builtin_nanf("");
@@ -1115,6 +1208,92 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   }
   put((gwbytes_t)a.theta, qc);
   if (a.reject_count && k == 0) a.reject_count[c] += a.n_traj - accepted;
+}
+
+// The row wave of an integrating wave (ROWS above): same lane, same chain, same coordinate.  It walks the groups of trajectories in
+// the integrator's order, one barrier in front of each, and owns the output side.  In the burn-in phase it stores no row (the
+// one-launch form rewrites the chain's slot of `theta` every trajectory; nobody reads those within the launch): only the final state.
+template <int D, int LB>
+__device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t gt, uint32_t lds) {
+  typedef float T;
+  constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
+  const bool on = (gt >> 2) < a.C;
+  const int64_t c = on ? gt >> 2 : a.C - 1;
+  const int k = (int)(gt & 3);
+  const int kk = k < D ? k : 0;                 // a dummy lane mirrors lane 0 (same address, same value)
+  const T mu = a.mu[kk];
+  T Qrow[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) Qrow[j] = eig[EIG_TOUT(D) + kk * D + j];
+  auto to_q = [&](T y) {                         // quad_body's: the same instructions in the same order
+    T q = mu;
+    asm volatile("s_nop 1" : "+v"(y));
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+      asm volatile("v_fmac_f32_dpp %0, %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf"
+                   : "+v"(q) : "v"(y), "v"(Qrow[j]), "n"(j));
+    return q;
+  };
+  const size_t C = (size_t)a.C;
+  const size_t el = (size_t)c * D + kk;
+  T qc = a.theta[el];
+  int32_t accepted = 0;
+  const uint32_t lds_both = 2u * lds + (uint32_t)(NU * 256);
+  const int n_burn = a.samples ? min(max(a.burn - a.traj_offset + 1, 0), a.n_traj) : a.n_traj;
+  T* row = nullptr;
+  auto take = [&](T m, bool q2) {               // one trajectory's message
+    const bool acc = __builtin_bit_cast(uint32_t, m) != QUAD_ROWS_REJECT;
+    const T q = to_q(m);                         // (every lane: the DPP operands come from the quad's other lanes)
+    qc = acc ? q : qc;
+    accepted += acc ? 1 : 0;
+    if (q2 && !acc) qc = a.theta_init[el];       // Q2: back to params_init itself
+    if (row) { if (on) row[el] = qc; row += C * D; }
+  };
+  auto group = [&](auto G, bool q2) {
+    asm volatile("s_barrier" ::: "memory");      // the integrator has filled this buffer
+    constexpr int g = decltype(G)::value;
+    if constexpr (g % 4 == 0) {
+      for (int i = 0; i < g; i += 4) {
+        T m0, m1, m2, m3;
+        asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:256\n\tds_read_b32 %2, %4 offset:512\n\tds_read_b32 %3, %4 offset:768\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(m0), "=&v"(m1), "=&v"(m2), "=&v"(m3) : "v"(lds + (uint32_t)i * 256u) : "memory");
+        take(m0, false); take(m1, false); take(m2, false); take(m3, false);
+      }
+    } else {
+      for (int i = 0; i < g; ++i) {
+        T m;
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(m) : "v"(lds + (uint32_t)i * 256u) : "memory");
+        take(m, q2);
+      }
+    }
+    lds = lds_both - lds;
+  };
+  std::integral_constant<int, 1> one;
+  int t = 0;
+  for (int phase = 0; phase < 2; ++phase) {
+    const int t_end = phase == 0 ? n_burn : a.n_traj;
+    if (phase == 1) {
+      row = a.samples ? a.samples + (size_t)max(a.traj_offset + t - a.burn, 1) * C * D : nullptr;
+      if (t < t_end && a.traj_offset + t == a.burn + 1) { group(one, true); t += 1; }
+    }
+    while (t + NU - 1 < t_end) { group(std::integral_constant<int, NU>{}, false); t += NU; }
+    while (t + NS - 1 < t_end) { group(std::integral_constant<int, NS>{}, false); t += NS; }
+    while (t < t_end) { group(one, false); t += 1; }
+  }
+  uint32_t starved;
+  asm volatile("s_barrier\n\tds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(starved) : "v"(lds) : "memory");
+  if (__builtin_expect(starved != 0u, 0)) {     // see QuadFused: the rows of this launch and the chain state become NaN
+    qc = __builtin_nanf("");
+    if (a.samples && on) {
+      const size_t r0 = (size_t)max(a.traj_offset + n_burn - a.burn, 1);
+      for (int tt = n_burn; tt < a.n_traj; ++tt) a.samples[(r0 + (size_t)(tt - n_burn)) * C * D + el] = qc;
+    }
+  }
+  if (on) {
+    a.theta[el] = qc;
+    if (a.reject_count && k == 0) a.reject_count[c] += a.n_traj - accepted;
+  }
 }
 
 template <int D, bool DIAG, int LB, int VAR = 0>
@@ -1162,9 +1341,17 @@ __device__ __forceinline__ void quad_fill_record(float* __restrict__ ws, int64_t
 // zeroes the counters for the next launch (no memset node, nothing the host has to track: the launch stays graph-capturable).
 constexpr int QUAD_FUSED_NT = 256;         // four waves per block: a producer block counts itself ONCE per chunk (the counter of a chunk
                                            // is one address: its atomic adds serialise - 512 one-wave producers were 3x slower than 128)
-template <int D, int LB>
-__global__ __launch_bounds__(QUAD_FUSED_NT) void hmc_gauss_quad_fused_kernel(GaussArgs<float> a, const float* __restrict__ eig, QuadFused fz,
-                                                                             int nc, int spc, uint32_t* done) {
+// NI (tuning key "quad_rows"): 0 = every consumer wave integrates and stores its rows itself (QUAD_FUSED_NT threads); NI > 0 = a block
+// of 2 NI waves, waves [0, NI) integrate, wave NI + w is the row wave of wave w (quad_body: ROWS).  A producer block writes the same
+// 256-record slices whatever the block size, so the records, the chunk counters and their target do not depend on NI.
+#ifndef QUAD_ROWS_NI
+#define QUAD_ROWS_NI 2                     // with two pairs per block the integrating waves and the row waves sit on different SIMDs of the
+#endif                                     // CU (waves of a workgroup are dealt out round robin) and the block size is the producers' own
+constexpr int quad_fused_threads(int NI) { return NI > 0 ? 128 * NI : QUAD_FUSED_NT; }
+template <int D, int LB, int NI = 0>
+__global__ __launch_bounds__(quad_fused_threads(NI)) void hmc_gauss_quad_fused_kernel(GaussArgs<float> a, const float* __restrict__ eig, QuadFused fz,
+                                                                                      int nc, int spc, uint32_t* done) {
+  constexpr int NT = quad_fused_threads(NI);
   if ((int)blockIdx.x >= nc) {
     // producer block b of spc: its slices of every chunk, chunk by chunk; one count per block and chunk
     const int b = (int)blockIdx.x - nc;
@@ -1172,16 +1359,35 @@ __global__ __launch_bounds__(QUAD_FUSED_NT) void hmc_gauss_quad_fused_kernel(Gau
     const int64_t per_chunk = (int64_t)fz.ch * a.C, total = (int64_t)a.n_traj * a.C;
     for (int chn = 0; chn < fz.nchunks; ++chn) {
       const int64_t base = (int64_t)chn * per_chunk, end = min(base + per_chunk, total);
-      for (int64_t idx = base + (int64_t)b * QUAD_FUSED_NT + threadIdx.x; idx < end; idx += (int64_t)spc * QUAD_FUSED_NT)
-        quad_fill_record<D>(a.ws_z, idx, a.C, a.traj_offset, a.seed, a.chain_offset, eig);
+      for (int sub = threadIdx.x; sub < QUAD_FUSED_NT; sub += NT)               // (NT = QUAD_FUSED_NT: once)
+        for (int64_t idx = base + (int64_t)b * QUAD_FUSED_NT + sub; idx < end; idx += (int64_t)spc * QUAD_FUSED_NT)
+          quad_fill_record<D>(a.ws_z, idx, a.C, a.traj_offset, a.seed, a.chain_offset, eig);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                          // this wave's records are acknowledged ...
       __syncthreads();                                                          // ... and so are the block's other waves' ...
       if (threadIdx.x == 0) __hip_atomic_fetch_add(fz.flags + chn, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... before they are counted
     }
     return;
   }
-  __builtin_amdgcn_s_setprio(3);                 // a consumer's time is its issue rate: it goes first where a producer shares its SIMD
-  quad_body<D, false, LB, 7, true>(a, eig, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, fz);
+  if constexpr (NI > 0) {
+    constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
+    __shared__ float ring[NI * 2 * NU * 64];       // per integrating wave: two buffers of NU positions x 64 lanes
+    const int wave = (int)(threadIdx.x >> 6), pair = wave < NI ? wave : wave - NI;
+    const uint32_t lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)ring + (uint32_t)(pair * 2 * NU * 256) + (uint32_t)(threadIdx.x & 63) * 4u;
+    const int64_t gt = ((int64_t)blockIdx.x * NI + pair) * 64 + (threadIdx.x & 63);
+    if (wave >= NI) { quad_rows_body<D, LB>(a, eig, gt, lds); return; }
+    __builtin_amdgcn_s_setprio(3);
+    quad_body<D, false, LB, 7, true, true>(a, eig, gt, fz, lds);
+  } else {
+    __builtin_amdgcn_s_setprio(3);                 // a consumer's time is its issue rate: it goes first where a producer shares its SIMD
+#if defined(QUAD_ABLATE_ROWS)      // timing only (profiles/r07a_quad_rows.txt): the integrator's side of ROWS with nobody reading the ring - the ceiling of the row wave
+    constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
+    __shared__ float ring[4 * 2 * NU * 64];
+    quad_body<D, false, LB, 7, true, true>(a, eig, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, fz,
+        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)ring + (uint32_t)((threadIdx.x >> 6) * 2 * NU * 256) + (uint32_t)(threadIdx.x & 63) * 4u);
+#else
+    quad_body<D, false, LB, 7, true>(a, eig, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, fz);
+#endif
+  }
   if (threadIdx.x == 0) {
     const uint32_t old = __hip_atomic_fetch_add(done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     if (old == (uint32_t)nc - 1u) {                                             // every consumer has read every chunk
@@ -1559,6 +1765,7 @@ int g_quad_producers = 64;   // tuning key "quad_producers": producer blocks (fo
 int g_quad_starve = 0;       // debug key "quad_starve": 1 = the producers of the fused launch leave without producing (exercises the consumers' bounded wait)
 constexpr int QUAD_STATUS_OFF = QUAD_FUSED_OFF + QUAD_FUSED_CHUNKS + 1;         // element of the eig block that holds the sticky status word
 static_assert(QUAD_STATUS_OFF < 128, "the status word lives in the eig block's free tail");
+int g_quad_rows = 1;         // tuning key "quad_rows" (default 1): the fused launch hands the sample rows to row waves through LDS (quad_body: ROWS); 0 = every consumer wave stores its own
 int g_quad_fused = 1;        // tuning key "quad_fused" (default 1): records produced inside the trajectory launch (prepared workspaces only); 0 = a pre-draw launch in front of it
 template <typename T> static bool eig_block_prepared(const GaussArgs<T>& a, int mass_kind);
 template <typename T> static bool quad_route(const GaussArgs<T>& a);
@@ -1602,7 +1809,9 @@ template <typename T, int D, int MASS> void launch_small(const GaussArgs<T>& a, 
           const int pmax = g_quad_producers * (int)((a.C + 1023) / 1024);                 // g_quad_producers per 1024 chains, each walks
           if (spc > pmax) spc = pmax;                                                     // its slices of every chunk
           fz.target = (uint32_t)spc;
-          const int qgrid = (int)((a.C * 4 + QUAD_FUSED_NT - 1) / QUAD_FUSED_NT);         // consumer blocks of this launch shape
+          constexpr int NI = QUAD_ROWS_NI;
+          const int cpb = g_quad_rows ? 64 * NI : QUAD_FUSED_NT;                           // chain lanes per consumer block ("quad_rows": NI integrating waves + NI row waves)
+          const int qgrid = (int)((a.C * 4 + cpb - 1) / cpb);                              // consumer blocks of this launch shape
           fz.flags = reinterpret_cast<uint32_t*>(a.ws_logu + QUAD_FUSED_OFF);
           uint32_t* done = fz.flags + QUAD_FUSED_CHUNKS;
           fz.err = done + 1;                                                                  // the sticky status word (QUAD_STATUS_OFF)
@@ -1610,7 +1819,14 @@ template <typename T, int D, int MASS> void launch_small(const GaussArgs<T>& a, 
           (void)W;
           note_route("hmc_gauss_quad_fused_kernel<%d,%d>", D, lbv);
           const int fgrid = qgrid + spc;
-          if (lbv == 25) hmc_gauss_quad_fused_kernel<D, 25><<<fgrid, QUAD_FUSED_NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);
+          if (g_quad_rows) {
+            constexpr int NT = quad_fused_threads(NI);
+            if (lbv == 25) hmc_gauss_quad_fused_kernel<D, 25, NI><<<fgrid, NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);
+            else if (lbv == 10) hmc_gauss_quad_fused_kernel<D, 10, NI><<<fgrid, NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);
+            else if (lbv == 5) hmc_gauss_quad_fused_kernel<D, 5, NI><<<fgrid, NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);
+            else hmc_gauss_quad_fused_kernel<D, 0, NI><<<fgrid, NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);
+          }
+          else if (lbv == 25) hmc_gauss_quad_fused_kernel<D, 25><<<fgrid, QUAD_FUSED_NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);
           else if (lbv == 10) hmc_gauss_quad_fused_kernel<D, 10><<<fgrid, QUAD_FUSED_NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);
           else if (lbv == 5) hmc_gauss_quad_fused_kernel<D, 5><<<fgrid, QUAD_FUSED_NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);
           else hmc_gauss_quad_fused_kernel<D, 0><<<fgrid, QUAD_FUSED_NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);

@@ -543,7 +543,10 @@ int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int it
  * route of hta_hmc_gaussian_sample produces its draw records inside the trajectory launch - producer blocks behind the consumer
  * blocks, write-through stores, one counter per chunk of whole trajectories, the consumers' look-ahead gated per pass - instead
  * of a pre-draw launch in front of it: bit-identical results, BASELINE config 2 0.175 -> 0.151 ms per call; 0 = the two-launch
- * form; "quad_producers": producer blocks of that launch per 1024 chains, 64; "quad_chunks": hand-over chunks per launch, 8). */
+ * form; "quad_producers": producer blocks of that launch per 1024 chains, 64; "quad_chunks": hand-over chunks per launch, 8),
+ * "quad_rows" (1 default = in that launch every integrating wave hands its trajectories' outcomes through LDS to a row wave of its
+ * block, which computes and stores the sample rows, the final state and the reject counts: bit-identical results, BASELINE config 2
+ * 0.148 -> 0.139 ms per call; 0 = every consumer wave stores its own rows, the parity partner). */
 int hta_set_tuning(const char* key, int value);
 /* current value of a route key; every key back to its default (test fixtures call this between tests: the keys are
  * process-global).  The environment variable HTA_TUNING_DEFAULTS="key=value,..." moves the DEFAULT of the named keys for the

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Disassembly of one gfx950 kernel out of a built object / shared library (CPU only: llvm-objdump).
 
-    python tools/isa_of.py hamiltorch_amd/csrc/build/hmc_gaussian.o 'hmc_gauss_quad_kernelILi3ELb0ELi25ELi0E' [--loops]
+    python tools/isa_of.py hamiltorch_amd/csrc/build/hmc_gaussian.o 'hmc_gauss_quad_kernelILi3ELb0ELi25ELi0E' [--loops] [--whole]
 
 Prints the kernel's instructions (addresses and encodings stripped).  --loops: for every backward branch the number of
 instructions of the loop it closes, split into the dependent FMA chain (v_fmac / v_fma / v_pk_fma), other vector ALU, scalar,
 memory and wait / nop instructions - the static cost model of a kernel that runs ONE wave per SIMD (every instruction of a
-lone wave takes an issue slot: DESIGN.md section 4, cfg2)."""
+lone wave takes an issue slot: DESIGN.md section 4, cfg2).  --whole: read on past the first s_endpgm, to the end of the symbol (a
+kernel whose waves take different roles and leave at different places: hmc_gauss_quad_fused_kernel<D, LB, NI>)."""
 import os
 import re
 import shutil
@@ -17,7 +18,7 @@ import tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def kernel_lines(path, pattern):
+def kernel_lines(path, pattern, whole=False):
     d = tempfile.mkdtemp(prefix="isa_of_")
     try:
         shutil.copy(path, os.path.join(d, "in.bin"))
@@ -39,7 +40,7 @@ def kernel_lines(path, pattern):
                     mm = re.match(r"^\s+(\S.*?)\s*//\s*([0-9A-F]+):", ln)
                     if mm:
                         out.append((int(mm.group(2), 16), mm.group(1).strip()))
-                        if mm.group(1).startswith("s_endpgm"):
+                        if mm.group(1).startswith("s_endpgm") and not whole:
                             break
             if out:
                 return name, out
@@ -90,7 +91,7 @@ def loops(lines):
 def main():
     if len(sys.argv) < 3:
         raise SystemExit(__doc__)
-    name, lines = kernel_lines(sys.argv[1], sys.argv[2])
+    name, lines = kernel_lines(sys.argv[1], sys.argv[2], "--whole" in sys.argv)
     if "--loops" in sys.argv:
         print(name, "-", len(lines), "instructions")
         for s, e in loops(lines):
