@@ -736,7 +736,8 @@ __global__ __launch_bounds__(256) void hmc_gauss_eig_kernel(GaussArgs<T> a, cons
 #endif
 // Developer builds only (profiles/r05y_quad_ablation.txt: timing of the trajectory's parts, wrong samples): -DQUAD_FUSED_NS=n -DQUAD_SLOTS=m (a deeper
 // record look-ahead: measured, no effect), -DQUAD_ABLATE_STORE / _LOAD / _ACC / _TAIL (one cost of a trajectory removed at a time),
-// -DQUAD_ABLATE_ROWS (profiles/r07a_quad_rows.txt: the integrating wave of "quad_rows" with nobody reading its ring), -DQUAD_ROWS_NI=1|4
+// -DQUAD_ABLATE_ROWS (profiles/r07a_quad_rows.txt: the integrating wave of "quad_rows" with nobody reading its ring), -DQUAD_ABLATE_LOCAL
+// (profiles/r08a_quad_local.txt: the local launch whose producer waves draw nothing), -DQUAD_ROWS_NI=1|4
 // (the other placements of the row waves: correct samples).
 #ifndef QUAD_SLOTS
 #define QUAD_SLOTS 4
@@ -784,6 +785,9 @@ template <int I, int N, typename F> __device__ __forceinline__ void quad_static_
 // launch and its slot of the chain state with NaN - the failure is in the data as well as in the word.  All of it is off the hot
 // path (inside the once-per-chunk poll and after the loops).  Debug key "quad_starve" makes the producers leave at once (the test
 // of this path: tests/test_gpu_hmc.py::test_fused_launch_reports_starved_producers).
+// The LOCAL launch (hmc_gauss_quad_local_kernel, tuning key "quad_local", the default for D <= 3 with row waves) has no such hand-over:
+// its producers are waves of the consumer's own block, behind a barrier.  It takes none of the fields below; "quad_starve" = 1 - a
+// producer BLOCK that is never scheduled - selects this cross-block launch, the only one that failure can happen to.
 struct QuadFused { uint32_t* flags; int ch; uint32_t target; int nchunks; uint32_t* err; int starve; };
 // ROWS (tuning key "quad_rows", default 1): the OUTPUT side of a chain - the proposal's row element q = mu + Tout y, the select of the
 // stored element, the row store, the final state, the reject count, the NaN rows of a starved launch - runs on a ROW WAVE of the
@@ -802,15 +806,37 @@ struct QuadFused { uint32_t* flags; int ch; uint32_t target; int nchunks; uint32
 //             derive the sequence of groups from the same launch arguments (quad_groups), so every wave of the block - also one
 //             whose chains lie past a.C: it integrates the last chain again and stores nothing - reaches every barrier.
 // Results are bit-identical to "quad_rows" = 0 (tests/test_gpu_quad_rows.py).
+// LOCAL (hmc_gauss_quad_local_kernel below) is ROWS with the record coming from LDS too: the refill between the two butterfly stages
+// is a ds_read_b32 at lane base + immediate, the producer waves join the group's barrier, and there is no need_rows.  <3, 25>: 67.6
+// instructions per trajectory, no global memory instruction in the pass (tests/test_quad_local_resources.py).
 constexpr int quad_fused_ns(int LB, bool FUSED) { return FUSED ? QUAD_FUSED_NS : (LB == 5 ? 4 : (LB == 10 ? 3 : 2)); }
 constexpr int quad_nu(int LB, int NS, bool UADDR) { return UADDR ? (LB == 25 ? (NS > 4 ? 4 : 8) : 4) * NS : 2 * NS; }
 constexpr uint32_t QUAD_ROWS_REJECT = 0xFFFFFFFFu;
-template <int D, bool DIAG, int LB, int VAR, bool FUSED, bool ROWS = false>
+// The groups of trajectories of a LOCAL launch (hmc_gauss_quad_local_kernel), in order: f(first trajectory, phase, size, Q2).  The
+// integrating wave, its row wave and the producer waves all walk THIS sequence, derived from the launch arguments alone, so every
+// wave of a block reaches the same barriers.  It is the fused launch's sequence (the Q2 trajectory alone, passes of NU, passes of
+// NS, single ones; per phase) with one short group of NS in front: the integrator starts after one producer sweep, not after a pass.
+template <int NS, int NU, typename F> __device__ __forceinline__ void quad_local_groups(const GaussArgs<float>& a, F&& f) {
+  const int n_burn = a.samples ? min(max(a.burn - a.traj_offset + 1, 0), a.n_traj) : a.n_traj;
+  std::integral_constant<int, 1> one;
+  std::false_type plain;
+  int t = 0;
+  for (int phase = 0; phase < 2; ++phase) {
+    const int t_end = phase == 0 ? n_burn : a.n_traj;
+    if (phase == 1 && t < t_end && a.traj_offset + t == a.burn + 1) { f(t, phase, one, std::true_type{}); t += 1; }
+    if (t == 0 && NS - 1 < t_end) { f(t, phase, std::integral_constant<int, NS>{}, plain); t += NS; }
+    while (t + NU - 1 < t_end) { f(t, phase, std::integral_constant<int, NU>{}, plain); t += NU; }
+    while (t + NS - 1 < t_end) { f(t, phase, std::integral_constant<int, NS>{}, plain); t += NS; }
+    while (t < t_end) { f(t, phase, one, plain); t += 1; }
+  }
+}
+template <int D, bool DIAG, int LB, int VAR, bool FUSED, bool ROWS = false, bool LOCAL = false>
 __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t gt, const QuadFused fz,
-                                          uint32_t lds = 0) {
+                                          uint32_t lds = 0, uint32_t recl = 0) {
   typedef float T;
   constexpr bool UADDR = (VAR & 1) != 0, NOGUARD = (VAR & 2) != 0, TAIL = (VAR & 4) != 0;
   static_assert(!ROWS || (FUSED && UADDR && TAIL && !DIAG), "the row-wave form is an instance of the fused launch");
+  static_assert(!LOCAL || (ROWS && D < 4), "the local launch is the row-wave form with one record vector");
   const bool on = (gt >> 2) < a.C;
   const int64_t c = ROWS ? (on ? gt >> 2 : a.C - 1) : gt >> 2;       // ROWS: every wave stays for the barriers
   const int k = (int)(gt & 3);
@@ -820,9 +846,9 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   int ready = 0;
   uint32_t pf = 0;
   bool starved = false;
-  if constexpr (FUSED) pf = __hip_atomic_load(fz.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (FUSED && !LOCAL) pf = __hip_atomic_load(fz.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   auto need_rows = [&](int upto) {              // rows up to `upto` are about to be read (rows >= n_traj are slack: never produced)
-    if constexpr (FUSED) {
+    if constexpr (FUSED && !LOCAL) {            // (LOCAL: the block's own producer waves, published by the barrier of the group)
       if (__builtin_expect(upto >= ready, 0)) {
         do {
           const int chn = ready / fz.ch;
@@ -903,11 +929,16 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   static_assert(NS <= QUAD_SLOTS_MAX, "workspace slack");
   T zs[NS], lus[NS];
   need_rows(NS - 1);
+  if constexpr (LOCAL) {
 #pragma unroll
-  for (int i = 0; i < NS; ++i) {
-    if (i) rec += rec_step;
-    zs[i] = *rec;
-    lus[i] = D == 4 ? *(rec + ushift) : 0.f;
+    for (int i = 0; i < NS; ++i) zs[i] = lus[i] = 0.f;      // (begin() below reads the first records of every group)
+  } else {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      if (i) rec += rec_step;
+      zs[i] = *rec;
+      lus[i] = D == 4 ? *(rec + ushift) : 0.f;
+    }
   }
   // Every lane stores once per trajectory, unconditionally (uniform vmcnt, see hmc_gauss_small_kernel).
   const uint32_t qoff = (uint32_t)(((size_t)c * D + kk) * sizeof(T));
@@ -919,7 +950,7 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   // (the dispatcher bounds C so that the offsets stay below 2^32)
   constexpr int NU = quad_nu(LB, NS, UADDR);       // trajectories per pass of the unrolled loop (the scalar bookkeeping of a pass is shared)
   // ROWS: the message of the trajectory at position i of a group goes to lds + 256 i (64 lanes x 4 bytes); `lds` flips between the two buffers
-  const uint32_t lds_both = 2u * lds + (uint32_t)(NU * 256);
+  const uint32_t lds_both = 2u * lds + (uint32_t)(NU * 256), recl_both = 2u * recl + (uint32_t)(NU * 256);
   T pend_y = 0.f;                                // the last trajectory's proposal and decision: its message is still to be written (D < 4)
   uint64_t pend_mask = 0;
   auto handover = [&](auto G) {                  // after a group of G trajectories
@@ -931,6 +962,19 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       lds = lds_both - lds;
+      if constexpr (LOCAL) recl = recl_both - recl;
+    }
+  };
+  // LOCAL: the record element of the trajectory at position i of a group is at recl + 256 i (16 chains x 16 bytes: this lane's element
+  // of its chain's record is the lane's own dword), in the buffer the producer waves filled during the previous group and the
+  // barrier in front of this one published.  A group reads its first NS elements here and, inside trajectory P, the element of
+  // trajectory P + NS - never past the group: the other buffer is being written.
+  typedef const __attribute__((address_space(3))) T* lrec_t;
+  auto begin = [&](auto G) {
+    if constexpr (LOCAL) {
+#pragma unroll
+      for (int i = 0; i < (decltype(G)::value < NS ? decltype(G)::value : NS); ++i)      // (volatile: four ds_read_b32, not two paired reads - the loop's count is pinned)
+        zs[i] = *(const volatile __attribute__((address_space(3))) T*)(uintptr_t)(recl + (uint32_t)i * 256u);
     }
   };
   typedef const __attribute__((address_space(1))) char* gcbytes_t;
@@ -962,7 +1006,7 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
     // unrolled by two over the slots, so the newest load is never touched by a register rotation)
     // `q2`: this is trajectory burn+1, the one the reference resets to params_init when it is rejected (S:1016-1018);
     // a separate instance, so that the others carry no check for it.
-    auto trajectory = [&](T& slot, T& slot_u, auto q2, auto pos) {
+    auto trajectory = [&](T& slot, T& slot_u, auto q2, auto pos, auto grp) {      // (grp: the size of the trajectory's group, LOCAL reads it)
       if constexpr (!UADDR) rec += rec_step;
       // everything that reads the record first, so that its register is free for the refill
       // ---- gibbs S:185-186 (rotated draws), H_old S:971, half kick S:281
@@ -1042,8 +1086,15 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
             asm volatile("v_mov_b32_dpp %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\ts_nop 0" "\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1" "\n\ts_nop 0"
                          : "+v"(dH), "=&v"(logu) : "v"(slot), "n"(D));
           }
+          if constexpr (LOCAL) {
+            // the refill is an LDS read the compiler sees and waits for (the message writes it does not see only make its count
+            // stricter: LDS returns in order); the last NS trajectories of a group have nothing to read and pad the wait state
+            if constexpr (P + NS < decltype(grp)::value) slot = *(lrec_t)(uintptr_t)(recl + (uint32_t)(P + NS) * 256u);
+            else asm volatile("s_nop 0");
+          } else {
           asm volatile("" : "+v"(roff[pos]));            // keeps the zero-extension next to its use: base + 32-bit offset addressing
           slot = *(grec_t)(recb + roff[pos]);
+          }
           // second stage, the compare and the selects of yc and potc in one block (the compiler pads a wait state between two blocks)
           asm volatile("v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_cmp_ge_f32_e64 %3, %0, %4\n\t"
                        "v_cndmask_b32_e64 %1, %1, %5, %3\n\tv_cndmask_b32_e64 %2, %2, %6, %3"
@@ -1153,44 +1204,55 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
       for (int i = 0; i + 1 < NS; ++i) { zs[i] = zs[i + 1]; lus[i] = lus[i + 1]; }
       zs[NS - 1] = z; lus[NS - 1] = u;
     };
-    if constexpr (UADDR) {
+    if constexpr (LOCAL) {
+      // the groups of the launch as every role of the block walks them (quad_local_groups); the barrier in front of the first
+      // group publishes its records
+      if (phase == 0) {
+        asm volatile("s_barrier" ::: "memory");
+        quad_local_groups<NS, NU>(a, [&](int, int, auto G, auto q2) {
+          begin(G);
+          quad_static_for<0, decltype(G)::value>([&](auto I) { trajectory(zs[I % NS], lus[I % NS], q2, I, G); });
+          handover(G);
+        });
+      }
+    } else if constexpr (UADDR) {
       // the same schedule with the bases moved once per group of trajectories
       auto moved = [&](int g) { recb += (size_t)g * (rec_step * sizeof(T)); row += (size_t)g * row_step; };
       // (FUSED: a pass of G trajectories starting at t prefetches the rows up to t + G - 1 + NS)
       if (phase == 1 && t < t_end && a.traj_offset + t == a.burn + 1) {
         need_rows(t + NS);
-        trajectory(zs[0], lus[0], std::true_type{}, first);
+        trajectory(zs[0], lus[0], std::true_type{}, first, first);
         moved(1);
         rotate();
         handover(std::integral_constant<int, 1>{});
       }
       while (t + NU - 1 < t_end) {
         need_rows(t + NU - 1 + NS);
-        quad_static_for<0, NU>([&](auto I) { trajectory(zs[I % NS], lus[I % NS], plain, I); });
+        quad_static_for<0, NU>([&](auto I) { trajectory(zs[I % NS], lus[I % NS], plain, I, first); });
         moved(NU);
         handover(std::integral_constant<int, NU>{});
       }
       while (t + NS - 1 < t_end) {
         need_rows(t + NS - 1 + NS);
-        quad_static_for<0, NS>([&](auto I) { trajectory(zs[I], lus[I], plain, I); });
+        quad_static_for<0, NS>([&](auto I) { trajectory(zs[I], lus[I], plain, I, first); });
         moved(NS);
         handover(std::integral_constant<int, NS>{});
       }
-      while (t < t_end) { need_rows(t + NS); trajectory(zs[0], lus[0], plain, first); moved(1); rotate(); handover(std::integral_constant<int, 1>{}); }
+      while (t < t_end) { need_rows(t + NS); trajectory(zs[0], lus[0], plain, first, first); moved(1); rotate(); handover(std::integral_constant<int, 1>{}); }
     } else {
       if (phase == 1 && t < t_end && a.traj_offset + t == a.burn + 1) {              // the Q2 trajectory opens the stored phase
-        trajectory(zs[0], lus[0], std::true_type{}, first);
+        trajectory(zs[0], lus[0], std::true_type{}, first, first);
         rotate();
       }
       while (t + 2 * NS - 1 < t_end) {            // unrolled over the slots (twice): no register rotation on the hot path
 #pragma unroll
-        for (int i = 0; i < 2 * NS; ++i) trajectory(zs[i % NS], lus[i % NS], plain, first);
+        for (int i = 0; i < 2 * NS; ++i) trajectory(zs[i % NS], lus[i % NS], plain, first, first);
       }
       if (t + NS - 1 < t_end) {
 #pragma unroll
-        for (int i = 0; i < NS; ++i) trajectory(zs[i], lus[i], plain, first);
+        for (int i = 0; i < NS; ++i) trajectory(zs[i], lus[i], plain, first, first);
       }
-      while (t < t_end) { trajectory(zs[0], lus[0], plain, first); rotate(); }
+      while (t < t_end) { trajectory(zs[0], lus[0], plain, first, first); rotate(); }
     }
   }
   if constexpr (ROWS) {                           // one more group: whether this wave's hand-over from the producers failed
@@ -1213,7 +1275,7 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
 // The row wave of an integrating wave (ROWS above): same lane, same chain, same coordinate.  It walks the groups of trajectories in
 // the integrator's order, one barrier in front of each, and owns the output side.  In the burn-in phase it stores no row (the
 // one-launch form rewrites the chain's slot of `theta` every trajectory; nobody reads those within the launch): only the final state.
-template <int D, int LB>
+template <int D, int LB, bool LOCAL = false>
 __device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t gt, uint32_t lds) {
   typedef float T;
   constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
@@ -1271,6 +1333,13 @@ __device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const 
   };
   std::integral_constant<int, 1> one;
   int t = 0;
+  if constexpr (LOCAL) {                          // the local launch's sequence (its first barrier publishes records: not this wave's business)
+    asm volatile("s_barrier" ::: "memory");
+    quad_local_groups<NS, NU>(a, [&](int t0, int phase, auto G, auto q2) {
+      if (phase == 1 && !row) row = a.samples + (size_t)max(a.traj_offset + t0 - a.burn, 1) * C * D;      // (the stored phase is empty without a.samples)
+      group(G, decltype(q2)::value);
+    });
+  } else
   for (int phase = 0; phase < 2; ++phase) {
     const int t_end = phase == 0 ? n_burn : a.n_traj;
     if (phase == 1) {
@@ -1301,16 +1370,16 @@ __global__ __launch_bounds__(64) void hmc_gauss_quad_kernel(GaussArgs<float> a, 
   quad_body<D, DIAG, LB, VAR, false>(a, eig, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, QuadFused{nullptr, 1, 0u, 0, nullptr, 0});
 }
 
-// one record (csrc: rng_fill_small_kernel's body): the draws of (trajectory t, chain c), rotated into the eigenbasis
+// one record (csrc: rng_fill_small_kernel's body): the draws of trajectory n of global chain `chain`, rotated into the eigenbasis, and
+// 2 log u in element D.  The ONE body of the record's arithmetic: the cross-block producers and the local launch's producer waves
+// both call it, so their records are the same bits.
 template <int D>
-__device__ __forceinline__ void quad_fill_record(float* __restrict__ ws, int64_t idx, int64_t C, int traj_offset, uint64_t seed,
-                                                 uint64_t chain_offset, const float* __restrict__ eig) {
+__device__ __forceinline__ void quad_make_record(uint64_t seed, uint64_t chain, uint32_t n, const float* __restrict__ eig,
+                                                 float (&rec)[rec_elems<float, D>()]) {
   typedef float T;
   constexpr int W = rec_elems<T, D>();
-  const int64_t t = idx / C, c = idx - t * C;
   T z[D], lu;
-  draw_inline<T, D>(seed, chain_offset + (uint64_t)c, (uint32_t)(traj_offset + (int)t), z, lu);
-  T rec[W];
+  draw_inline<T, D>(seed, chain, n, z, lu);
 #pragma unroll
   for (int i = 0; i < W; ++i) rec[i] = 0;
 #pragma unroll
@@ -1321,6 +1390,15 @@ __device__ __forceinline__ void quad_fill_record(float* __restrict__ ws, int64_t
     rec[kk] = acc;
   }
   rec[D] = 2.0f * lu;
+}
+template <int D>
+__device__ __forceinline__ void quad_fill_record(float* __restrict__ ws, int64_t idx, int64_t C, int traj_offset, uint64_t seed,
+                                                 uint64_t chain_offset, const float* __restrict__ eig) {
+  typedef float T;
+  constexpr int W = rec_elems<T, D>();
+  const int64_t t = idx / C, c = idx - t * C;
+  T rec[W];
+  quad_make_record<D>(seed, chain_offset + (uint64_t)c, (uint32_t)(traj_offset + (int)t), eig, rec);
   // write-through stores at agent scope (sc1): the record is in memory, visible to the consumers' XCDs, once the store is
   // acknowledged - no L2 write-back per producer block (a buffer_wbl2 per 64 records made the producers 40x slower)
   // (one 16-byte store with the agent-scope bit: four dword stores quadrupled the write transactions)
@@ -1397,6 +1475,61 @@ __global__ __launch_bounds__(quad_fused_threads(NI)) void hmc_gauss_quad_fused_k
   }
 }
 
+
+// LOCAL (tuning key "quad_local", default 1; D <= 3): the records of a block's chains are drawn by producer waves of THAT block and
+// handed over through LDS - no record travels through memory, no chunk counter, no poll, no wait for chunk 0, and the launch does
+// not depend on any other block being resident (the HAND-OVER FAILURE of QuadFused cannot happen: waves of one workgroup are
+// co-resident by construction).  One block = 16 chains, four waves, one per SIMD:
+//   wave 0     integrates (quad_body: ROWS, LOCAL): its record element is a ds_read_b32 at lane base + position x 256
+//   wave 1     its row wave (quad_rows_body)
+//   waves 2-3  produce: lane (position % 8, chain) computes quad_make_record's record - the cross-block producer's arithmetic - and
+//              writes it with one 16-byte LDS write to [position][chain]
+//   ring       next to the message ring, two record buffers of one pass (NU positions x 16 chains x 16 bytes)
+//   hand-over  the barrier per group of the row-wave protocol, joined by the producers: while the integrator runs group g they fill
+//              buffer (g + 1) % 2 with the records of group g + 1, and the barrier between the two groups publishes it; one more
+//              barrier in front of the first group.  All roles walk quad_local_groups.
+// Results are bit-identical to the cross-block launch (tests/test_gpu_quad_local.py).  -DQUAD_ABLATE_LOCAL (developer builds, timing
+// only, wrong samples: profiles/r08a_quad_local.txt): the producer waves draw nothing - the ceiling of the integrator's side.
+template <int D, int LB>
+__device__ __forceinline__ void quad_local_produce(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t c0, const uint32_t recl,
+                                                   const int pl) {
+  constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
+  static_assert(rec_elems<float, D>() == 4, "one 16-byte record");
+  typedef float V4f __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(3))) V4f* lvec_t;
+  (void)(lvec_t)nullptr;
+  const int chain = pl & 15, p0 = pl >> 4;                                      // 128 lanes: eight positions of 16 chains per sweep
+  const int64_t c = min(c0 + chain, a.C - 1);                                   // (past a.C: the last chain again, as the integrator does)
+  const uint64_t gchain = a.chain_offset + (uint64_t)c;
+  uint32_t dst = recl + (uint32_t)(p0 * 256 + chain * 16);
+  const uint32_t dst_both = 2u * dst + (uint32_t)(NU * 256);
+  quad_local_groups<NS, NU>(a, [&](int t0, int, auto G, auto) {
+#if !defined(QUAD_ABLATE_LOCAL)
+    for (int p = p0; p < decltype(G)::value; p += 8) {
+      float rec[4];
+      quad_make_record<D>(a.seed, gchain, (uint32_t)(a.traj_offset + t0 + p), eig, rec);
+      *(lvec_t)(uintptr_t)(dst + (uint32_t)((p - p0) * 256)) = V4f{rec[0], rec[1], rec[2], rec[3]};
+    }
+#endif
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // publishes this group's records
+    dst = dst_both - dst;
+  });
+  asm volatile("s_barrier\n\ts_barrier" ::: "memory");                          // the last group's hand-over and the status message: the other roles'
+}
+template <int D, int LB>
+__global__ __launch_bounds__(256) void hmc_gauss_quad_local_kernel(GaussArgs<float> a, const float* __restrict__ eig) {
+  constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
+  __shared__ __attribute__((aligned(16))) float ring[2 * NU * 64 + 2 * NU * 64];      // messages (64 lanes x 4 bytes) | records (16 chains x 16 bytes), two passes each
+  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+  const uint32_t msgs = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)ring, recs = msgs + (uint32_t)(2 * NU * 256);
+  const int64_t gt = (int64_t)blockIdx.x * 64 + lane;
+  if (wave == 0) {
+    __builtin_amdgcn_s_setprio(3);
+    quad_body<D, false, LB, 7, true, true, true>(a, eig, gt, QuadFused{nullptr, 1, 0u, 0, nullptr, 0}, msgs + (uint32_t)lane * 4u, recs + (uint32_t)lane * 4u);
+  }
+  else if (wave == 1) quad_rows_body<D, LB, true>(a, eig, gt, msgs + (uint32_t)lane * 4u);
+  else quad_local_produce<D, LB>(a, eig, (int64_t)blockIdx.x * 16, recs, (int)threadIdx.x - 128);
+}
 
 template <typename T, int D, int MASS>
 __global__ void leapfrog_gauss_small_kernel(GaussArgs<T> a) {
@@ -1766,6 +1899,7 @@ int g_quad_starve = 0;       // debug key "quad_starve": 1 = the producers of th
 constexpr int QUAD_STATUS_OFF = QUAD_FUSED_OFF + QUAD_FUSED_CHUNKS + 1;         // element of the eig block that holds the sticky status word
 static_assert(QUAD_STATUS_OFF < 128, "the status word lives in the eig block's free tail");
 int g_quad_rows = 1;         // tuning key "quad_rows" (default 1): the fused launch hands the sample rows to row waves through LDS (quad_body: ROWS); 0 = every consumer wave stores its own
+int g_quad_local = 1;        // tuning key "quad_local" (default 1): with "quad_rows" and D <= 3 the records are drawn by producer waves of the consumer's own block (hmc_gauss_quad_local_kernel); 0 = producer blocks behind the consumers', the parity partner
 int g_quad_fused = 1;        // tuning key "quad_fused" (default 1): records produced inside the trajectory launch (prepared workspaces only); 0 = a pre-draw launch in front of it
 template <typename T> static bool eig_block_prepared(const GaussArgs<T>& a, int mass_kind);
 template <typename T> static bool quad_route(const GaussArgs<T>& a);
@@ -1819,7 +1953,17 @@ template <typename T, int D, int MASS> void launch_small(const GaussArgs<T>& a, 
           (void)W;
           note_route("hmc_gauss_quad_fused_kernel<%d,%d>", D, lbv);
           const int fgrid = qgrid + spc;
-          if (g_quad_rows) {
+          // "quad_starve" emulates a producer BLOCK that is never scheduled - a failure the local launch cannot have - so it selects the cross-block launch
+          if (D <= 3 && g_quad_rows && g_quad_local && !g_quad_starve) {
+            if constexpr (D <= 3) {
+              const int lgrid = (int)((a.C + 15) / 16);                                       // 16 chains per block; the record area of the workspace stays unused
+              if (lbv == 25) hmc_gauss_quad_local_kernel<D, 25><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+              else if (lbv == 10) hmc_gauss_quad_local_kernel<D, 10><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+              else if (lbv == 5) hmc_gauss_quad_local_kernel<D, 5><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+              else hmc_gauss_quad_local_kernel<D, 0><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+            }
+          }
+          else if (g_quad_rows) {
             constexpr int NT = quad_fused_threads(NI);
             if (lbv == 25) hmc_gauss_quad_fused_kernel<D, 25, NI><<<fgrid, NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);
             else if (lbv == 10) hmc_gauss_quad_fused_kernel<D, 10, NI><<<fgrid, NT, 0, s>>>(a, a.ws_logu, fz, qgrid, spc, done);

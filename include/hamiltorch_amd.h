@@ -546,7 +546,12 @@ int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int it
  * form; "quad_producers": producer blocks of that launch per 1024 chains, 64; "quad_chunks": hand-over chunks per launch, 8),
  * "quad_rows" (1 default = in that launch every integrating wave hands its trajectories' outcomes through LDS to a row wave of its
  * block, which computes and stores the sample rows, the final state and the reject counts: bit-identical results, BASELINE config 2
- * 0.148 -> 0.139 ms per call; 0 = every consumer wave stores its own rows, the parity partner). */
+ * 0.148 -> 0.139 ms per call; 0 = every consumer wave stores its own rows, the parity partner),
+ * "quad_local" (1 default = with "quad_rows" and D <= 3 the draw records are made by producer waves of the consumer's own block and
+ * handed over through LDS - 16 chains per block: one integrating wave, its row wave, two producer waves - so no record travels
+ * through memory and the launch does not wait for other blocks; the record area of the workspace stays unused, the status word stays
+ * 0: bit-identical results, BASELINE config 2 0.139 -> 0.132 ms per call; 0 = producer blocks behind the consumers' blocks, the parity
+ * partner; the debug key "quad_starve" = 1 selects that cross-block launch as well). */
 int hta_set_tuning(const char* key, int value);
 /* current value of a route key; every key back to its default (test fixtures call this between tests: the keys are
  * process-global).  The environment variable HTA_TUNING_DEFAULTS="key=value,..." moves the DEFAULT of the named keys for the
