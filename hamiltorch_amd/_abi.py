@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhamiltorch_amd.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 MASS_NONE, MASS_DIAG, MASS_FULL = 0, 1, 2
 
@@ -56,6 +56,12 @@ class HtaCbRmhmcArgs(ctypes.Structure):
                 ("accept", c_vp), ("lp_out", c_vp), ("C", ctypes.c_longlong), ("eps", c_f64), ("alpha", c_f64), ("jitter", c_f64),
                 ("omega", c_f64), ("seed", c_u64), ("chain_offset", c_u64), ("L", c_int), ("n_traj", c_int), ("traj_offset", c_int),
                 ("burn", c_int)]
+
+
+class HtaCbPathArgs(ctypes.Structure):
+    """csrc/jit/jit_args.h: HtaCbPathArgs."""
+    _fields_ = [("theta0", c_vp), ("p0", c_vp), ("inv_mass", c_vp), ("path_theta", c_vp), ("path_p", c_vp), ("lp_end", c_vp),
+                ("C", ctypes.c_longlong), ("eps", c_f64), ("seed", c_u64), ("steps", c_int), ("split_kind", c_int)]
 
 
 class HtaCbDerivArgs(ctypes.Structure):
@@ -113,7 +119,8 @@ PLAIN_SYMBOLS = ["hta_abi_version", "hta_last_error", "hta_device_info", "hta_se
                  "hta_metric_eval_workspace_bytes", "hta_netn_hmc_workspace_bytes",
                  "hta_jit_available", "hta_jit_last_log", "hta_jit_note_fallback", "hta_jit_compile", "hta_jit_free", "hta_jit_load", "hta_jit_unload",
                  "hta_jit_module_info", "hta_jit_hmc_workspace_bytes", "hta_jit_hmc_predraw_bytes", "hta_jit_hmc_sample", "hta_jit_derivs",
-                 "hta_jit_rmhmc_workspace_bytes", "hta_jit_rmhmc_sample", "hta_jit_split_workspace_bytes", "hta_jit_split_sample"]
+                 "hta_jit_rmhmc_workspace_bytes", "hta_jit_rmhmc_sample", "hta_jit_split_workspace_bytes", "hta_jit_split_sample",
+                 "hta_jit_path_leapfrog"]
 TYPED_SYMBOLS = sorted(_sig(c_f32).keys())
 
 
@@ -182,6 +189,7 @@ def load():
         lib.hta_jit_split_workspace_bytes.argtypes = [c_i64, c_int, c_int]
         lib.hta_jit_split_workspace_bytes.restype = c_i64
         lib.hta_jit_split_sample.argtypes = [c_vp, ctypes.POINTER(HtaCbHmcArgs), c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp]
+        lib.hta_jit_path_leapfrog.argtypes = [c_vp, ctypes.POINTER(HtaCbPathArgs), c_int, c_int, c_int, c_int, c_int, c_vp]
         for suf, scalar in (("f32", c_f32), ("f64", c_f64)):
             for name, args in _sig(scalar).items():
                 fn = getattr(lib, "%s_%s" % (name, suf))

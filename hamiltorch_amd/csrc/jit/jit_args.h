@@ -4,7 +4,7 @@
 #ifndef HTA_JIT_ARGS_H
 #define HTA_JIT_ARGS_H
 
-#define HTA_CB_INFO_WORDS 8 /* hta_cb_info[]: {magic, D, sizeof(T), mass kind, kernel set, n_nodes, n_nodes3 (RMHMC) | M (split), 0} */
+#define HTA_CB_INFO_WORDS 8 /* hta_cb_info[]: {magic, D, sizeof(T), mass kind, kernel set, n_nodes, n_nodes3 (RMHMC) | M (split; path: M, 0 = one callable), 0} */
 #define HTA_CB_MAGIC 0x48544131 /* "HTA1" */
 
 /* kernel sets (hta_cb_info[4]): which entry points the module exports */
@@ -12,6 +12,7 @@
 #define HTA_CB_SET_DERIVS 2 /* hta_cb_derivs_kernel + hta_cb_contract_kernel (Riemannian)   */
 #define HTA_CB_SET_RMHMC 3  /* hta_cb_rmhmc_kernel: explicit RMHMC trajectories, D <= 16     */
 #define HTA_CB_SET_SPLIT 4  /* hta_cb_split_kernel: split HMC on a LIST of callables          */
+#define HTA_CB_SET_PATH 5   /* hta_cb_path_kernel | hta_cb_split_path_kernel (info[6] = M | 0): leapfrog paths */
 
 #define HTA_CB_MAX_SPLIT 16 /* subsets of a compiled list (a subset order packs into 64 bits) */
 /* HtaCbHmcArgs::split_kind = HTA_SPLIT_SYMMETRIC / _RAND / _KMID of include/hamiltorch_amd.h */
@@ -56,6 +57,21 @@ typedef struct HtaCbRmhmcArgs {
   unsigned long long seed, chain_offset;
   int L, n_traj, traj_offset, burn;
 } HtaCbRmhmcArgs;
+
+/* hta_jit_path_leapfrog (csrc/jit/path_callback.hip.in): every step of one leapfrog call, nothing drawn, nothing decided */
+typedef struct HtaCbPathArgs {
+  const void* theta0;   /* [C, D] start points                                                        */
+  const void* p0;       /* [C, D] start momenta                                                       */
+  const void* inv_mass; /* (D,) | (D,D) | NULL                                                        */
+  void* path_theta;     /* [steps, C, D]: theta after every step                                      */
+  void* path_p;         /* [steps, C, D]: p after every step (plain HMC: the last row after S:302)    */
+  void* lp_end;         /* [C] log p at the end points (a list: the sum over the subsets), or NULL    */
+  long long C;
+  double eps;
+  unsigned long long seed; /* SPLITTING_RAND: the subset order is hta::split_permutation(seed, 0, M)  */
+  int steps;
+  int split_kind;       /* hta_cb_split_path_kernel: HTA_CB_SPLIT_*; 0 for a single callable          */
+} HtaCbPathArgs;
 
 typedef struct HtaCbDerivArgs {
   const void* theta; /* [C, D]                                              */

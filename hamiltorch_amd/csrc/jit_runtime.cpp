@@ -3,7 +3,8 @@
 // hamiltorch_amd/jit/ traces a user log_prob_func (the callback contract of hamiltorch/samplers.py:272-274), writes its
 // value / derivatives as straight-line device code and hands the SOURCE here; the hand-written kernels it is compiled into
 // live under csrc/jit/ (hmc_callback.hip.in: the reference's sample() loop for plain HMC, samplers.py:965-1026, around that
-// function; split_callback.hip.in: the same loop around a LIST of them under the split integrators, samplers.py:494-596; derivs_callback.hip.in: the derivatives the Riemannian samplers ask torch.func for, samplers.py:108, :397-398).
+// function; split_callback.hip.in: the same loop around a LIST of them under the split integrators, samplers.py:494-596;
+// path_callback.hip.in: the per-step path of ONE leapfrog() call, samplers.py:281-302 / :494-596, around either; derivs_callback.hip.in: the derivatives the Riemannian samplers ask torch.func for, samplers.py:108, :397-398).
 //
 // Boundary rules as everywhere else: device pointers are the caller's, launches are enqueued on the caller's stream, nothing is
 // synchronised on the launch path.  Compiling (hta_jit_compile) is host work and returns a malloc'ed code object; loading
@@ -65,7 +66,7 @@ thread_local std::string g_jit_log;
 
 struct Module {
   hipModule_t mod = nullptr;
-  hipFunction_t hmc = nullptr, predraw = nullptr, derivs = nullptr, contract = nullptr, rmhmc = nullptr, split = nullptr;
+  hipFunction_t hmc = nullptr, predraw = nullptr, derivs = nullptr, contract = nullptr, rmhmc = nullptr, split = nullptr, path = nullptr;
   int info[HTA_CB_INFO_WORDS] = {};
   int device = -1;
 };
@@ -190,6 +191,8 @@ int hta_jit_load(const void* code, int64_t bytes, void** module_out) {
     e = hipModuleGetFunction(&m->rmhmc, m->mod, "hta_cb_rmhmc_kernel");
   } else if (m->info[4] == HTA_CB_SET_SPLIT) {
     e = hipModuleGetFunction(&m->split, m->mod, "hta_cb_split_kernel");
+  } else if (m->info[4] == HTA_CB_SET_PATH) {
+    e = hipModuleGetFunction(&m->path, m->mod, m->info[6] > 0 ? "hta_cb_split_path_kernel" : "hta_cb_path_kernel");
   } else {
     e = hipErrorInvalidValue;
   }
@@ -292,6 +295,43 @@ int hta_jit_split_sample(void* module, const HtaCbHmcArgs* args, int D, int M, i
              split_kind == HTA_CB_SPLIT_RAND ? "rand" : split_kind == HTA_CB_SPLIT_KMID ? "kmid" : "symmetric", m->info[5]);
   profile_begin((hipStream_t)stream);
   const int rc = launch(m->split, "hta_jit_split_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
+  profile_end((hipStream_t)stream);
+  return rc;
+}
+
+/* Every step of ONE leapfrog call on a compiled callable (M == 0) or a compiled list of M callables under a split integrator
+ * (csrc/jit/path_callback.hip.in): what samplers.leapfrog() returns for a (C, D) batch, in one launch. */
+int hta_jit_path_leapfrog(void* module, const HtaCbPathArgs* args, int D, int M, int itemsize, int mass_kind, int split_kind,
+                          void* stream) {
+  using namespace hta;
+  Module* m = (Module*)module;
+  HTA_REQUIRE(args && args->theta0 && args->p0 && args->C > 0 && args->steps >= 0 && D > 0 && (itemsize == 4 || itemsize == 8),
+              "hta_jit_path_leapfrog: bad arguments");
+  HTA_REQUIRE(M >= 0 && M <= HTA_CB_MAX_SPLIT, "hta_jit_path_leapfrog: %d subsets (0 = a single callable, at most %d)", M, HTA_CB_MAX_SPLIT);
+  HTA_REQUIRE(mass_kind == HTA_MASS_NONE || mass_kind == HTA_MASS_DIAG || mass_kind == HTA_MASS_FULL, "hta_jit_path_leapfrog: mass kind %d",
+              mass_kind);
+  HTA_REQUIRE(mass_kind == HTA_MASS_NONE || args->inv_mass, "hta_jit_path_leapfrog: inv_mass is NULL");
+  if (M > 0) {
+    HTA_REQUIRE(split_kind == HTA_CB_SPLIT_SYMMETRIC || split_kind == HTA_CB_SPLIT_RAND || split_kind == HTA_CB_SPLIT_KMID,
+                "hta_jit_path_leapfrog: split kind %d", split_kind);
+    HTA_REQUIRE(M >= 2 || split_kind == HTA_CB_SPLIT_RAND, "hta_jit_path_leapfrog: the symmetric schemes need more than one subset (S:497-498)");
+  } else {
+    HTA_REQUIRE(split_kind == 0, "hta_jit_path_leapfrog: a single callable has no split kind (%d)", split_kind);
+  }
+  HTA_REQUIRE(args->steps == 0 || (args->path_theta && args->path_p), "hta_jit_path_leapfrog: the path buffers are NULL");
+  if (args->steps == 0) return HTA_OK;          // an empty path: nothing to launch, whatever the module
+  if (int rc = check_module(m, "hta_jit_path_leapfrog", D, itemsize, mass_kind, HTA_CB_SET_PATH)) return rc;
+  HTA_REQUIRE(m->info[6] == M, "hta_jit_path_leapfrog: the module was compiled for %d subsets, the call has %d", m->info[6], M);
+  HtaCbPathArgs a = *args;
+  a.split_kind = M > 0 ? split_kind : 0;
+  const char* mass = mass_kind == HTA_MASS_NONE ? "none" : mass_kind == HTA_MASS_DIAG ? "diag" : "full";
+  if (M > 0)
+    note_route("hta_cb_split_path_kernel<D=%d,M=%d,%s,mass=%s,%s>", D, M, itemsize == 4 ? "f32" : "f64", mass,
+               split_kind == HTA_CB_SPLIT_RAND ? "rand" : split_kind == HTA_CB_SPLIT_KMID ? "kmid" : "symmetric");
+  else
+    note_route("hta_cb_path_kernel<D=%d,%s,mass=%s>", D, itemsize == 4 ? "f32" : "f64", mass);
+  profile_begin((hipStream_t)stream);
+  const int rc = launch(m->path, "hta_jit_path_leapfrog", a.C, &a, sizeof(a), (hipStream_t)stream);
   profile_end((hipStream_t)stream);
   return rc;
 }

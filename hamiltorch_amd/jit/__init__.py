@@ -11,7 +11,8 @@ GPU ~38 eager launches per step around kernels that take microseconds.  This pac
   runtime.py  hipRTC (through the C ABI: ``hta_jit_compile`` / ``hta_jit_load``) builds that text INTO the hand-written
               kernels of ``csrc/jit/`` - for plain HMC the whole ``sample()`` loop, one chain per lane, one launch per block
               of trajectories; for the split integrators (``log_prob_func`` is a LIST of callables, one per data subset) the
-              same loop around all of them: ``compile_split``, ``csrc/jit/split_callback.hip.in``.
+              same loop around all of them: ``compile_split``, ``csrc/jit/split_callback.hip.in``; for ``leapfrog()`` on a
+              batch of chains the per-step path of either: ``compile_path``, ``csrc/jit/path_callback.hip.in``.
 
 No inductor, no Triton, no code from torch's compiler stack beyond the tracer.  A callable the tracer or the lowering table
 does not cover (data-dependent control flow, the tuple / ``pass_grad`` protocols, unlisted operations, graphs that are too
@@ -78,14 +79,53 @@ def _signature(fn):
     return sig, objs
 
 
-class CompiledHMC:
-    """A traced callable compiled into the HMC trajectory kernel for one (D, dtype, mass kind)."""
+class CompiledPath:
+    """A traced callable, or a list of them, compiled into the leapfrog-path kernel (csrc/jit/path_callback.hip.in) for one
+    (D, dtype, mass kind); `M` is the length of the list, 0 for a single callable."""
 
     def __init__(self, traced, key, blob, dtype, mass_kind):
         self.traced, self.key, self.blob, self.dtype, self.mass_kind = traced, key, blob, dtype, mass_kind
 
+    @property
+    def M(self):
+        return len(self.traced) if isinstance(self.traced, list) else 0
+
     def module(self, device):
         return runtime.module_for(self.key, self.blob, device)
+
+
+class CompiledHMC:
+    """A traced callable compiled into the HMC trajectory kernel for one (D, dtype, mass kind).  The generated text is kept; the
+    code objects around it are built when first asked for - `key` / `blob`: the trajectory kernel's (at once by compile_hmc and
+    its siblings), `path()`: the leapfrog-path kernel's (compile_path) - so that a trace made for one serves the other."""
+
+    def __init__(self, traced, generated, skeleton, dtype, mass_kind):
+        self.traced, self.generated, self.skeleton, self.dtype, self.mass_kind = traced, generated, skeleton, dtype, mass_kind
+        self._code = self._path = None
+
+    def _built(self):
+        if self._code is None:
+            self._code = runtime.compile_source(self.generated, self.skeleton)
+        return self._code
+
+    @property
+    def key(self):
+        return self._built()[0]
+
+    @property
+    def blob(self):
+        return self._built()[1]
+
+    def module(self, device):
+        return runtime.module_for(self.key, self.blob, device)
+
+    def path(self):
+        if self.skeleton not in (runtime.SKELETON_HMC, runtime.SKELETON_SPLIT):
+            raise Unsupported("leapfrog paths are compiled for plain HMC and the split integrators only")
+        if self._path is None:
+            key, blob = runtime.compile_source(self.generated, runtime.SKELETON_PATH)
+            self._path = CompiledPath(self.traced, key, blob, self.dtype, self.mass_kind)
+        return self._path
 
 
 class CompiledDerivs(CompiledHMC):
@@ -111,7 +151,32 @@ def compile_rmhmc(fn, example, dtype, jitter, fresh=False):
     return _compile(fn, example, dtype, "rmhmc-jitter" if jitter else "rmhmc", fresh)
 
 
-def _compile(fn, example, dtype, mass_kind, fresh):
+def compile_path(fn_or_list, example, dtype, mass_kind, fresh=False):
+    """CompiledPath for a callable (plain HMC) or a list of callables (the split integrators) at points shaped like the (D,) tensor
+    ``example``: what ``samplers.leapfrog`` runs a (C, D) batch of chains on; raises ``Unsupported``.  Traces go through the cache
+    of ``compile_hmc`` / ``compile_split`` - a callable already traced for ``sample()`` is not traced again, only the path module
+    is built (and a callable first seen here is not traced again by ``sample()``); every new trace is checked against
+    torch.autograd like theirs."""
+    if isinstance(fn_or_list, (list, tuple)):
+        return compile_split(fn_or_list, example, dtype, mass_kind, fresh, _path=True)
+    return _compile(fn_or_list, example, dtype, int(mass_kind), fresh, path=True)
+
+
+def _finish(out, path):
+    """Build the code object the caller asked for (the trajectory kernel's, or the path kernel's) around a compiled entry.  hipRTC turning
+    the generated text down (an emitter bug, a device function hipRTC lacks) is not the user's problem: the callable runs on the
+    previous path, the reason (the compiler's first error line) is reported like any other refusal."""
+    try:
+        if path:
+            return out.path()
+        out._built()
+        return out
+    except runtime.CompileError as e:
+        first = next((ln for ln in e.log.splitlines() if "error" in ln), str(e).splitlines()[0])
+        raise Unsupported("hipRTC rejected the generated code: %s" % first.strip()[:160]) from None
+
+
+def _compile(fn, example, dtype, mass_kind, fresh, path=False):
     _note("")
     cfg = (int(example.numel()), dtype, mass_kind, example.device.type)
     sig = objs = None
@@ -127,31 +192,23 @@ def _compile(fn, example, dtype, mass_kind, fresh):
         if isinstance(ent[2], Unsupported):
             _note(str(ent[2]))
             raise ent[2]
-        return ent[2]
+        return _hit(ent[2], path)
     try:
         traced = trace_callback(fn, example)
         stats["traced"] += 1
         _check_against_autograd(traced, fn, example)
         if mass_kind == "derivs":
-            key, blob = runtime.compile_source(runtime.derivs_generated_source(traced, dtype), runtime.SKELETON_DERIVS)
-            out = CompiledDerivs(traced, key, blob, dtype, mass_kind)
+            out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype), runtime.SKELETON_DERIVS, dtype, mass_kind)
         elif mass_kind in ("rmhmc", "rmhmc-jitter"):
-            key, blob = runtime.compile_source(runtime.derivs_generated_source(traced, dtype, mass_kind == "rmhmc-jitter"), runtime.SKELETON_RMHMC)
-            out = CompiledDerivs(traced, key, blob, dtype, mass_kind)
+            out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype, mass_kind == "rmhmc-jitter"), runtime.SKELETON_RMHMC,
+                                 dtype, mass_kind)
         else:
-            key, blob = runtime.compile_source(runtime.hmc_generated_source(traced, dtype, mass_kind), runtime.SKELETON_HMC)
-            out = CompiledHMC(traced, key, blob, dtype, mass_kind)
+            out = CompiledHMC(traced, runtime.hmc_generated_source(traced, dtype, mass_kind), runtime.SKELETON_HMC, dtype, mass_kind)
+        ret = _finish(out, path)
     except Unsupported as e:
         stats["unsupported"] += 1
         _note(str(e))
         out = e
-    except runtime.CompileError as e:
-        # hipRTC turned the generated text down (an emitter bug, a device function hipRTC lacks): not the user's problem - the callable
-        # runs on the previous path, the reason (the compiler's first error line) is reported like any other refusal
-        stats["unsupported"] += 1
-        first = next((ln for ln in e.log.splitlines() if "error" in ln), str(e).splitlines()[0])
-        out = Unsupported("hipRTC rejected the generated code: %s" % first.strip()[:160])
-        _note(str(out))
     if sig is not None:
         try:
             with _lock:
@@ -160,7 +217,16 @@ def _compile(fn, example, dtype, mass_kind, fresh):
             pass
     if isinstance(out, Unsupported):
         raise out
-    return out
+    return ret
+
+
+def _hit(out, path):
+    """A cached entry for a caller that may want the other of its two code objects (built now, once)."""
+    try:
+        return _finish(out, path)
+    except Unsupported as e:
+        _note(str(e))
+        raise
 
 
 class CompiledSplit(CompiledHMC):
@@ -172,7 +238,7 @@ class CompiledSplit(CompiledHMC):
         return len(self.traced)
 
 
-def compile_split(fns, example, dtype, mass_kind, fresh=False):
+def compile_split(fns, example, dtype, mass_kind, fresh=False, _path=False):
     """CompiledSplit for the list of callables ``fns`` (Integrator.SPLITTING / SPLITTING_RAND / SPLITTING_KMID: one callable per
     data subset) at points shaped like the (D,) tensor ``example``; raises ``Unsupported``.  Every callable is traced and checked
     against torch.autograd like a single one; one unsupported subset makes the whole list unsupported, and the reason names it.
@@ -199,7 +265,7 @@ def compile_split(fns, example, dtype, mass_kind, fresh=False):
         if isinstance(ent[2], Unsupported):
             _note(str(ent[2]))
             raise ent[2]
-        return ent[2]
+        return _hit(ent[2], _path)
     try:
         if not fns:
             raise Unsupported("an empty list of callables")
@@ -216,17 +282,12 @@ def compile_split(fns, example, dtype, mass_kind, fresh=False):
             except Unsupported as e:
                 raise Unsupported("subset %d: %s" % (m, e)) from None
             traced.append(tr)
-        key, blob = runtime.compile_source(runtime.split_generated_source(traced, dtype, mass_kind), runtime.SKELETON_SPLIT)
-        out = CompiledSplit(traced, key, blob, dtype, mass_kind)
+        out = CompiledSplit(traced, runtime.split_generated_source(traced, dtype, mass_kind), runtime.SKELETON_SPLIT, dtype, mass_kind)
+        ret = _finish(out, _path)
     except Unsupported as e:
         stats["unsupported"] += 1
         _note(str(e))
         out = e
-    except runtime.CompileError as e:
-        stats["unsupported"] += 1
-        first = next((ln for ln in e.log.splitlines() if "error" in ln), str(e).splitlines()[0])
-        out = Unsupported("hipRTC rejected the generated code: %s" % first.strip()[:160])
-        _note(str(out))
     if sig is not None:
         try:
             with _lock:
@@ -235,7 +296,7 @@ def compile_split(fns, example, dtype, mass_kind, fresh=False):
             pass
     if isinstance(out, Unsupported):
         raise out
-    return out
+    return ret
 
 
 def _check_against_autograd(traced, fn, example, points=4):

@@ -22,6 +22,7 @@ _HEADERS = (("cb_math.hpp", "jit/cb_math.hpp"), ("philox.hpp", "philox.hpp"), ("
             ("jit_args.h", "jit/jit_args.h"), ("cb_hmc_shared.hpp", "jit/cb_hmc_shared.hpp"))
 SKELETON_HMC = "jit/hmc_callback.hip.in"
 SKELETON_SPLIT = "jit/split_callback.hip.in"
+SKELETON_PATH = "jit/path_callback.hip.in"
 SKELETON_DERIVS = "jit/derivs_callback.hip.in"
 SKELETON_RMHMC = "jit/rmhmc_callback.hip.in"
 # (SLP vectorisation ON: the straight-line callback code packs into v_pk_mul / v_pk_fma pairs - 67 -> 59 instructions per
@@ -247,6 +248,33 @@ def split_final_logp(workspace, C, dtype):
     """Sum of the subsets' log p at the state the last launch ended in ([C] view of the workspace)."""
     item = torch.empty((), dtype=dtype).element_size()
     return workspace[:C * item].view(dtype)
+
+
+# ---- leapfrog paths (samplers.leapfrog on a batch of chains) -----------------------------------------------------------
+def path_generated_source(traced_or_list, dtype, mass_kind):
+    """The generated include of csrc/jit/path_callback.hip.in: that of the trajectory kernels, text for text - a traced callable
+    gives hmc_generated_source (hta_cb_path_kernel), a list of them split_generated_source (hta_cb_split_path_kernel) - with
+    their limits and refusals."""
+    if isinstance(traced_or_list, (list, tuple)):
+        return split_generated_source(list(traced_or_list), dtype, mass_kind)
+    return hmc_generated_source(traced_or_list, dtype, mass_kind)
+
+
+def path_leapfrog(module, theta0, p0, M, split_kind, mass_kind, inv_mass, steps, eps, seed, path_theta, path_p, lp_end=None):
+    """hta_jit_path_leapfrog: every step of one leapfrog call from (theta0, p0) [C, D] into path_theta / path_p [steps, C, D] and
+    log p at the end points into lp_end [C], one launch.  M = 0: a single callable; else a list of M under split_kind."""
+    _abi.require_device(theta0, "params")
+    C, D = theta0.shape
+    a = _abi.HtaCbPathArgs()
+    a.theta0, a.p0 = theta0.data_ptr(), _abi._p(p0, theta0).value
+    a.inv_mass = None if inv_mass is None else _abi._p(inv_mass, theta0).value
+    a.path_theta, a.path_p = _abi._p(path_theta, theta0).value, _abi._p(path_p, theta0).value
+    a.lp_end = None if lp_end is None else _abi._p(lp_end, theta0).value
+    a.C, a.eps, a.seed = C, float(eps), int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.steps, a.split_kind = int(steps), int(split_kind)
+    with torch.cuda.device(theta0.device):
+        _abi._check(_abi.load().hta_jit_path_leapfrog(module.handle, ctypes.byref(a), D, int(M), theta0.element_size(), int(mass_kind),
+                                                      int(split_kind), _abi._stream(theta0)), "hta_jit_path_leapfrog")
 
 
 # ---- derivatives for the Riemannian samplers ---------------------------------------------------------------------------

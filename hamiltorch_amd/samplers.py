@@ -277,7 +277,16 @@ def leapfrog(params, momentum, log_prob_func, steps=10, step_size=0.1, jitter=0.
              fixed_point_max_iterations=6, jitter_max_tries=10, inv_mass=None, ham_func=None, sampler=Sampler.HMC,
              integrator=Integrator.IMPLICIT, metric=Metric.HESSIAN, store_on_GPU=True, debug=False, pass_grad=None):
     """Same contract as the reference: returns (ret_params, ret_momenta), lists with one entry
-    per step (explicit RMHMC: ``[list, params_copy], [list, momentum_copy]``, S:462)."""
+    per step (explicit RMHMC: ``[list, params_copy], [list, momentum_copy]``, S:462).
+
+    Sampler.HMC with a 2-D ``params`` (a (C, D) batch of chains) and a callable the callback compiler takes - or, under
+    SPLITTING / SPLITTING_RAND / SPLITTING_KMID, a list of them - is integrated in ONE launch with value and gradient inlined,
+    a chain per lane, every step's (theta, p) stored (``hta_cb_path_kernel`` / ``hta_cb_split_path_kernel``).  ONLY a 2-D
+    ``params`` takes that route: a (D,) ``params`` (one chain) keeps the torch-evaluated route bit for bit - the reference's own
+    tests compare its results with ``torch.eq``, and building a kernel for seconds buys nothing for one chain.  Gaussian targets,
+    ``pass_grad``, ``HAMILTORCH_AMD_JIT=0`` and callables the compiler refuses run as before; ``hta_last_route()`` says why.  The
+    compiled result is checked against the callable itself at the end points of up to 128 chains (``HAMILTORCH_AMD_JIT_VERIFY=0``
+    skips that): a mismatch on a reused trace traces again once, a second one warns and returns the torch-evaluated result."""
     theta, one = _as_batch(params)
     p, _ = _as_batch(momentum, "momentum")
     _abi.require_device(theta, "params")
@@ -291,6 +300,9 @@ def leapfrog(params, momentum, log_prob_func, steps=10, step_size=0.1, jitter=0.
             pp = torch.empty_like(pt)
             _abi.hmc_gaussian_leapfrog(theta, p, tgt.precision, tgt.mean, kind, im, steps, step_size, pt, pp)
             return [unb(t) for t in pt.unbind(0)], [unb(t) for t in pp.unbind(0)]
+        out = _compiled_path(log_prob_func, theta, p, one, pass_grad, steps, step_size, inv_mass)
+        if out is not None:
+            return out
         cb = _BatchedCallback(log_prob_func, pass_grad)
         ret_t, ret_p = [], []
         g, _ = cb.grad(theta)
@@ -313,10 +325,14 @@ def leapfrog(params, momentum, log_prob_func, steps=10, step_size=0.1, jitter=0.
             raise RuntimeError('For splitting log_prob_func must be list of functions')      # S:466-467
         if pass_grad is not None:
             raise RuntimeError('Passing user-determined gradients not implemented for splitting')  # S:468-469
+        # S:549: one subset order per leapfrog call
+        seed = util.next_stream_seed() if integrator == Integrator.SPLITTING_RAND else 0
+        out = _compiled_path(log_prob_func, theta, p, one, None, steps, step_size, inv_mass, integrator, seed)
+        if out is not None:
+            return out
         cbs = [_BatchedCallback(f) for f in log_prob_func]
         kind, im, _ = _mass_operands(inv_mass, theta)
-        # S:549: one subset order per leapfrog call
-        perm = util.split_permutation(util.next_stream_seed(), 0, len(cbs)) if integrator == Integrator.SPLITTING_RAND else None
+        perm = util.split_permutation(seed, 0, len(cbs)) if integrator == Integrator.SPLITTING_RAND else None
         ret_t, ret_p = [], []
         carry = None
         for _ in range(steps):
@@ -337,6 +353,76 @@ def leapfrog(params, momentum, log_prob_func, steps=10, step_size=0.1, jitter=0.
         return rmhmc.implicit_leapfrog(params, momentum, log_prob_func, steps, step_size, jitter, softabs_const, metric,
                                        fixed_point_threshold, fixed_point_max_iterations)
     raise NotImplementedError("Integrator.S3 (semi-separable Hamiltonians through a user ham_func) is outside the accelerated path")
+
+
+def _compiled_path(log_prob_func, theta, p, one, pass_grad, steps, step_size, inv_mass, integrator=None, seed=0):
+    """leapfrog() on the callback compiler's path kernel: (ret_params, ret_momenta), or None - the caller then runs the
+    torch-evaluated route, and the reason is in hta_last_route().  `integrator`: a split kind (log_prob_func is a list), else None."""
+    from . import jit
+    note = _abi.load().hta_jit_note_fallback
+    split = integrator is not None
+    fns = list(log_prob_func) if split else [log_prob_func]
+    reason = None
+    if one:
+        reason = "one chain: the reference's path"
+    elif pass_grad is not None:
+        reason = "pass_grad supplies the gradient"
+    elif not fns or not all(callable(f) for f in fns):
+        reason = "not a list of callables" if split else "not a callable"
+    elif not jit.enabled():
+        reason = "HAMILTORCH_AMD_JIT=0"
+    elif split and isinstance(inv_mass, list):
+        reason = "block-list inv_mass under a split integrator"
+    elif split and len(fns) == 1 and integrator != Integrator.SPLITTING_RAND:
+        reason = "one subset: the symmetric split schemes need more"       # (the torch-evaluated route raises S:497-498)
+    elif steps < 1:
+        reason = "no steps"
+    if reason is not None:
+        note(reason.encode())
+        return None
+    kind, im, _ = _mass_operands(inv_mass, theta)
+    C, D = theta.shape
+    for attempt in (0, 1):
+        before = jit.stats["trace_hits"]
+        try:
+            comp = jit.compile_path(fns if split else fns[0], theta[0], theta.dtype, kind, fresh=attempt == 1)
+        except jit.Unsupported as e:
+            note(str(e)[:140].encode("utf-8", "replace"))
+            return None
+        reused = jit.stats["trace_hits"] > before
+        pt = torch.empty((steps, C, D), dtype=theta.dtype, device=theta.device)
+        pp = torch.empty_like(pt)
+        lp_end = torch.empty(C, dtype=theta.dtype, device=theta.device)
+        jit.runtime.path_leapfrog(comp.module(theta.device), theta, p, comp.M, _SPLIT_KIND_OF[integrator] if split else 0, kind, im,
+                                  steps, step_size, seed, pt, pp, lp_end)
+        if _path_verified(fns, pt[-1], lp_end):
+            return list(pt.unbind(0)), list(pp.unbind(0))
+        # the compiled code disagrees with the callable(s) at the end points: a reused trace whose captured state changed in
+        # place (trace again, once), or a callable that is not a pure function of its argument - the rule of sample()
+        if not reused:
+            break
+    warnings.warn("hamiltorch_amd: the compiled form of %r disagrees with the callable itself at the end points of the path; "
+                  "integrating on the torch-evaluated callback path" % (log_prob_func,))
+    note(b"compiled code disagrees with the callable")
+    return None
+
+
+def _path_verified(fns, theta_end, lp_end, k=128):
+    """The path kernel's log p at the end points against the callable(s) evaluated by torch on up to `k` chains: the check and the
+    tolerances of _CompiledHMC.verify (non-finite reference values are exempt in the same way)."""
+    from . import jit
+    if os.environ.get("HAMILTORCH_AMD_JIT_VERIFY", "1") == "0":
+        return True
+    idx = slice(0, min(theta_end.shape[0], k))
+    mine = lp_end[idx]
+    ref = None
+    for fn in fns:
+        v = jit.torch_logp(fn, theta_end[idx]).to(mine.dtype).reshape(-1)
+        ref = v if ref is None else ref + v
+    fin_a, fin_b = torch.isfinite(mine), torch.isfinite(ref)
+    tol = (2e-4 if mine.dtype == torch.float32 else 1e-9)
+    close = (mine - ref).abs() <= tol * (10.0 + ref.abs())
+    return bool(((fin_a == fin_b) & (close | ~fin_b)).all())
 
 
 def _split_step(theta, p, cbs, eps, kind, im, integrator=Integrator.SPLITTING, perm=None, carry=None):

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HTA_ABI_VERSION 12
+#define HTA_ABI_VERSION 13
 
 #define HTA_OK 0
 #define HTA_ERR_INVALID (-1)   /* bad argument                           */
@@ -429,7 +429,7 @@ int hta_net_forward_f64(const double* theta, int64_t S, int n_layers, const int*
  *                     messages.  HTA_ERR_UNSUPPORTED: libhiprtc.so is not loadable.
  *   hta_jit_load      code object -> module on the CURRENT device (a preparation step: reads the module's info block back
  *                     once); hta_jit_unload frees it.  hta_jit_module_info: {magic, D, sizeof(T), mass kind, kernel set,
- *                     scalar operations, third-order operations (RMHMC) | M (split), 0}.
+ *                     scalar operations, third-order operations (RMHMC) | M (split; path: M, or 0 for one callable), 0}.
  *   hta_jit_hmc_sample  trajectories [traj_offset, traj_offset + n_traj) of plain HMC for C chains; the argument block is
  *                     HtaCbHmcArgs (csrc/jit/jit_args.h; `gcur` / `lp_out` are placed in `workspace`,
  *                     hta_jit_hmc_workspace_bytes(C, D, itemsize) bytes).  Same streams, rules and outputs as the pieces
@@ -439,6 +439,15 @@ int hta_net_forward_f64(const double* theta, int64_t S, int n_layers, const int*
  *                     once each and dispatched by a wave-uniform branch.  HtaCbHmcArgs with `split_kind`; `pre` must be NULL;
  *                     `lp_out` is placed in `workspace` (hta_jit_split_workspace_bytes(C, D, itemsize) bytes).  D / M /
  *                     itemsize / mass_kind must be the module's.
+ *   hta_jit_path_leapfrog  (ABI 13) every step of ONE leapfrog() call (S:281-302; a list under the split integrators: S:494-596) for C
+ *                     chains on a compiled callable (M = 0, split_kind = 0) or a compiled list of M callables:
+ *                     csrc/jit/path_callback.hip.in, a module of its own (kernel set HTA_CB_SET_PATH; info[6] = M | 0) built from
+ *                     the same generated text as the trajectory kernels.  HtaCbPathArgs: (theta0, p0) in, path_theta / path_p
+ *                     [steps, C, D] and lp_end[C] (log p at the end points, or NULL) out; nothing is drawn, nothing is decided,
+ *                     non-finite values stay in their chain's rows.  `seed` orders the subsets under HTA_CB_SPLIT_RAND
+ *                     (split_permutation(seed, 0, M), one order per call).  The arguments are checked first, steps == 0 then
+ *                     returns HTA_OK without a launch; D / M / itemsize / mass_kind must be the module's (else
+ *                     HTA_ERR_INVALID, nothing is launched).  No workspace.
  *   hta_jit_derivs    which = 0: logp[C], grad[C,D], neg_hess[C,D,D] (each optional) at theta[C,D]; which = 1:
  *                     contract[C,D] = d_k < Hess log p, M > with M[C,D,D] held fixed.
  *   hta_jit_note_fallback  records in hta_last_route() WHY a callable was not compiled (the caller then runs the pieces path).
@@ -463,6 +472,8 @@ int hta_jit_hmc_sample(void* module, const HtaCbHmcArgs* args, int D, int itemsi
 int64_t hta_jit_split_workspace_bytes(int64_t C, int D, int itemsize);
 int hta_jit_split_sample(void* module, const HtaCbHmcArgs* args, int D, int M, int itemsize, int mass_kind, int split_kind,
                          void* workspace, int64_t workspace_bytes, void* stream);
+int hta_jit_path_leapfrog(void* module, const HtaCbPathArgs* args, int D, int M, int itemsize, int mass_kind, int split_kind,
+                          void* stream);
 int hta_jit_derivs(void* module, const HtaCbDerivArgs* args, int which, int D, int itemsize, void* stream);
 /* Explicit RMHMC (S:389-462 inside the RMHMC branch of sample(), S:969-1026; Metric.SOFTABS) for a GENERAL target of small dimension
  * (D <= 16) on a compiled callable: trajectories [traj_offset, traj_offset + n_traj), a chain per lane, the 8 L + 3 metric evaluations
