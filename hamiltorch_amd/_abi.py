@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhamiltorch_amd.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 MASS_NONE, MASS_DIAG, MASS_FULL = 0, 1, 2
 
@@ -48,6 +48,11 @@ class HtaCbHmcArgs(ctypes.Structure):
                 ("C", ctypes.c_longlong), ("eps", c_f64), ("seed", c_u64), ("chain_offset", c_u64), ("L", c_int),
                 ("n_traj", c_int), ("traj_offset", c_int), ("burn", c_int), ("resume", c_int), ("split_kind", c_int), ("pre", c_vp),
                 ("pre_bytes", ctypes.c_longlong)]
+
+
+class HtaCbRolledArgs(ctypes.Structure):
+    """csrc/jit/jit_args.h: HtaCbRolledArgs (the fields of HtaCbHmcArgs, then the groups' tables)."""
+    _fields_ = HtaCbHmcArgs._fields_ + [("table", c_vp * 4), ("rows", c_int * 4), ("waves", c_int)]
 
 
 class HtaCbRmhmcArgs(ctypes.Structure):
@@ -120,7 +125,7 @@ PLAIN_SYMBOLS = ["hta_abi_version", "hta_last_error", "hta_device_info", "hta_se
                  "hta_jit_available", "hta_jit_last_log", "hta_jit_note_fallback", "hta_jit_compile", "hta_jit_free", "hta_jit_load", "hta_jit_unload",
                  "hta_jit_module_info", "hta_jit_hmc_workspace_bytes", "hta_jit_hmc_predraw_bytes", "hta_jit_hmc_sample", "hta_jit_derivs",
                  "hta_jit_rmhmc_workspace_bytes", "hta_jit_rmhmc_sample", "hta_jit_split_workspace_bytes", "hta_jit_split_sample",
-                 "hta_jit_path_leapfrog"]
+                 "hta_jit_path_leapfrog", "hta_jit_rolled_sample"]
 TYPED_SYMBOLS = sorted(_sig(c_f32).keys())
 
 
@@ -182,6 +187,7 @@ def load():
         lib.hta_jit_hmc_predraw_bytes.argtypes = [c_i64, c_int, c_int, c_int]
         lib.hta_jit_hmc_predraw_bytes.restype = c_i64
         lib.hta_jit_hmc_sample.argtypes = [c_vp, ctypes.POINTER(HtaCbHmcArgs), c_int, c_int, c_int, c_vp, c_i64, c_vp]
+        lib.hta_jit_rolled_sample.argtypes = [c_vp, ctypes.POINTER(HtaCbRolledArgs), c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp]
         lib.hta_jit_derivs.argtypes = [c_vp, ctypes.POINTER(HtaCbDerivArgs), c_int, c_int, c_int, c_vp]
         lib.hta_jit_rmhmc_workspace_bytes.argtypes = [c_i64, c_int, c_int]
         lib.hta_jit_rmhmc_workspace_bytes.restype = c_i64

@@ -4,7 +4,7 @@
 #ifndef HTA_JIT_ARGS_H
 #define HTA_JIT_ARGS_H
 
-#define HTA_CB_INFO_WORDS 8 /* hta_cb_info[]: {magic, D, sizeof(T), mass kind, kernel set, n_nodes, n_nodes3 (RMHMC) | M (split; path: M, 0 = one callable), 0} */
+#define HTA_CB_INFO_WORDS 8 /* hta_cb_info[]: {magic, D, sizeof(T), mass kind, kernel set, n_nodes, n_nodes3 (RMHMC) | M (split; path: M, 0 = one callable) | U (rolled), 0 | groups (rolled)} */
 #define HTA_CB_MAGIC 0x48544131 /* "HTA1" */
 
 /* kernel sets (hta_cb_info[4]): which entry points the module exports */
@@ -13,6 +13,10 @@
 #define HTA_CB_SET_RMHMC 3  /* hta_cb_rmhmc_kernel: explicit RMHMC trajectories, D <= 16     */
 #define HTA_CB_SET_SPLIT 4  /* hta_cb_split_kernel: split HMC on a LIST of callables          */
 #define HTA_CB_SET_PATH 5   /* hta_cb_path_kernel | hta_cb_split_path_kernel (info[6] = M | 0): leapfrog paths */
+#define HTA_CB_SET_ROLLED 6 /* hta_cb_rolled_kernel: plain HMC on a callable rolled over its data rows (info[6] = U, info[7] = groups) */
+
+#define HTA_CB_MAX_GROUPS 4       /* rolled groups of one callable (HtaCbRolledArgs::table / rows)                         */
+#define HTA_CB_ROLLED_LDS 65536   /* bytes of dynamic LDS of one workgroup of hta_cb_rolled_kernel at most                  */
 
 #define HTA_CB_MAX_SPLIT 16 /* subsets of a compiled list (a subset order packs into 64 bits) */
 /* HtaCbHmcArgs::split_kind = HTA_SPLIT_SYMMETRIC / _RAND / _KMID of include/hamiltorch_amd.h */
@@ -42,6 +46,32 @@ typedef struct HtaCbHmcArgs {
                               filled by hta_cb_predraw_kernel in front of the trajectory kernel (hta_jit_hmc_predraw_bytes)       */
   long long pre_bytes;
 } HtaCbHmcArgs;
+
+/* hta_jit_rolled_sample (csrc/jit/rolled_callback.hip.in): the fields of HtaCbHmcArgs, in their order, then the groups' tables */
+typedef struct HtaCbRolledArgs {
+  void* cur;
+  const void* init;
+  const void* inv_mass;
+  const void* mass_factor;
+  void* samples;
+  int* reject_count;
+  void* H_old;
+  void* H_new;
+  unsigned char* accept;
+  void* gcur;
+  void* lp_out;
+  long long C;
+  double eps;
+  unsigned long long seed, chain_offset;
+  int L, n_traj, traj_offset, burn;
+  int resume;
+  int split_kind;          /* 0 */
+  void* pre;
+  long long pre_bytes;
+  const void* table[HTA_CB_MAX_GROUPS]; /* [rows[k], slots of group k] per-row constants in the run's dtype, row-major; unused groups NULL */
+  int rows[HTA_CB_MAX_GROUPS];          /* rows of group k (> 0 for the module's groups)                                             */
+  int waves;               /* W: waves per workgroup of 64 chains, 1 | 2 | 4 | 8 | 16; wave w takes rows [w ceil(rows / W), ...) */
+} HtaCbRolledArgs;
 
 typedef struct HtaCbRmhmcArgs {
   void* cur;             /* [C, D] current state, in / out                                     */

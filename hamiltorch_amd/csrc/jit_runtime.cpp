@@ -66,7 +66,9 @@ thread_local std::string g_jit_log;
 
 struct Module {
   hipModule_t mod = nullptr;
-  hipFunction_t hmc = nullptr, predraw = nullptr, derivs = nullptr, contract = nullptr, rmhmc = nullptr, split = nullptr, path = nullptr;
+  hipFunction_t hmc = nullptr, predraw = nullptr, derivs = nullptr, contract = nullptr, rmhmc = nullptr, split = nullptr, path = nullptr,
+                rolled = nullptr;
+  int rolled_max_threads = 0;       // the launch bound hta_cb_rolled_kernel was built with
   int info[HTA_CB_INFO_WORDS] = {};
   int device = -1;
 };
@@ -85,10 +87,12 @@ int check_module(const Module* m, const char* who, int D, int itemsize, int mass
   return HTA_OK;
 }
 
-int launch(hipFunction_t fn, const char* who, int64_t C, void* args, size_t bytes, hipStream_t s, unsigned block = 64) {
+int launch(hipFunction_t fn, const char* who, int64_t C, void* args, size_t bytes, hipStream_t s, unsigned block = 64,
+           unsigned per_block = 0, unsigned lds = 0) {
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-  const unsigned grid = (unsigned)((C + block - 1) / block);
-  hipError_t e = hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, s, nullptr, config);
+  if (per_block == 0) per_block = block;        // (the rolled kernel: several waves of a block work on the same 64 chains)
+  const unsigned grid = (unsigned)((C + per_block - 1) / per_block);
+  hipError_t e = hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, lds, s, nullptr, config);
   if (e != hipSuccess) {
     set_error("%s: launch failed: %s", who, hipGetErrorString(e));
     return HTA_ERR_LAUNCH;
@@ -191,6 +195,10 @@ int hta_jit_load(const void* code, int64_t bytes, void** module_out) {
     e = hipModuleGetFunction(&m->rmhmc, m->mod, "hta_cb_rmhmc_kernel");
   } else if (m->info[4] == HTA_CB_SET_SPLIT) {
     e = hipModuleGetFunction(&m->split, m->mod, "hta_cb_split_kernel");
+  } else if (m->info[4] == HTA_CB_SET_ROLLED) {
+    e = hipModuleGetFunction(&m->rolled, m->mod, "hta_cb_rolled_kernel");
+    if (e == hipSuccess) e = hipModuleGetFunction(&m->predraw, m->mod, "hta_cb_predraw_kernel");
+    if (e == hipSuccess) e = hipFuncGetAttribute(&m->rolled_max_threads, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, m->rolled);
   } else if (m->info[4] == HTA_CB_SET_PATH) {
     e = hipModuleGetFunction(&m->path, m->mod, m->info[6] > 0 ? "hta_cb_split_path_kernel" : "hta_cb_path_kernel");
   } else {
@@ -257,6 +265,60 @@ int hta_jit_hmc_sample(void* module, const HtaCbHmcArgs* args, int D, int itemsi
   int rc = HTA_OK;
   if (a.pre) rc = launch(m->predraw, "hta_jit_hmc_sample (pre-draw)", a.C * (int64_t)a.n_traj, &a, sizeof(a), (hipStream_t)stream, 256);
   if (rc == HTA_OK) rc = launch(m->hmc, "hta_jit_hmc_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
+  profile_end((hipStream_t)stream);
+  return rc;
+}
+
+/* Plain HMC on a callable ROLLED over its data rows (csrc/jit/rolled_callback.hip.in): a workgroup is 64 chains x args->waves waves,
+ * the rows of every group divided over the waves, their partial sums added in wave order through LDS.  The arguments are checked
+ * before the module is looked at: a bad wave count, a NULL table, an empty group or an LDS request beyond the bound launch nothing. */
+int hta_jit_rolled_sample(void* module, const HtaCbRolledArgs* args, int D, int U, int groups, int itemsize, int mass_kind,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+  using namespace hta;
+  Module* m = (Module*)module;
+  HTA_REQUIRE(args && args->cur && args->init && args->reject_count && args->C > 0 && args->L >= 0 && args->n_traj >= 0 && D > 0 &&
+                  (itemsize == 4 || itemsize == 8),
+              "hta_jit_rolled_sample: bad arguments");
+  HTA_REQUIRE(U >= 0 && groups >= 1 && groups <= HTA_CB_MAX_GROUPS, "hta_jit_rolled_sample: %d groups (1 .. %d), %d uniforms", groups,
+              HTA_CB_MAX_GROUPS, U);
+  const int W = args->waves;
+  HTA_REQUIRE(W == 1 || W == 2 || W == 4 || W == 8 || W == 16, "hta_jit_rolled_sample: %d waves per workgroup (1, 2, 4, 8 or 16)", W);
+  for (int k = 0; k < groups; ++k) {
+    HTA_REQUIRE(args->table[k], "hta_jit_rolled_sample: the table of group %d is NULL", k);
+    HTA_REQUIRE(args->rows[k] > 0, "hta_jit_rolled_sample: group %d has %d rows", k, args->rows[k]);
+  }
+  const int64_t lds = (int64_t)W * 64 * (1 + D + U) * itemsize;
+  HTA_REQUIRE(lds <= HTA_CB_ROLLED_LDS, "hta_jit_rolled_sample: %d waves x 64 lanes x (1 + %d + %d) values of %d bytes = %lld bytes of LDS (limit %d)",
+              W, D, U, itemsize, (long long)lds, HTA_CB_ROLLED_LDS);
+  HTA_REQUIRE(mass_kind == HTA_MASS_NONE || (args->inv_mass && args->mass_factor), "hta_jit_rolled_sample: mass operands are NULL");
+  if (int rc = check_module(m, "hta_jit_rolled_sample", D, itemsize, mass_kind, HTA_CB_SET_ROLLED)) return rc;
+  HTA_REQUIRE(m->info[6] == U && m->info[7] == groups, "hta_jit_rolled_sample: the module was compiled for %d uniforms and %d groups, the call has %d and %d",
+              m->info[6], m->info[7], U, groups);
+  HTA_REQUIRE(W * 64 <= m->rolled_max_threads, "hta_jit_rolled_sample: %d waves per workgroup, the kernel was built for %d", W,
+              m->rolled_max_threads / 64);
+  HTA_REQUIRE(workspace && workspace_bytes >= hta_jit_hmc_workspace_bytes(args->C, D, itemsize),
+              "hta_jit_rolled_sample: workspace of %lld bytes, %lld needed (hta_jit_hmc_workspace_bytes)", (long long)workspace_bytes,
+              (long long)hta_jit_hmc_workspace_bytes(args->C, D, itemsize));
+  HTA_REQUIRE(!args->pre || args->pre_bytes >= hta_jit_hmc_predraw_bytes(args->C, D, args->n_traj, itemsize),
+              "hta_jit_rolled_sample: pre-draw buffer of %lld bytes, %lld needed (hta_jit_hmc_predraw_bytes)", (long long)args->pre_bytes,
+              (long long)hta_jit_hmc_predraw_bytes(args->C, D, args->n_traj, itemsize));
+  if (args->n_traj == 0) return HTA_OK;
+  HtaCbRolledArgs a = *args;
+  a.resume = args->resume ? 1 : 0;
+  a.split_kind = 0;
+  a.gcur = workspace;
+  a.lp_out = (char*)workspace + args->C * D * itemsize;
+  int max_rows = 0;
+  for (int k = 0; k < HTA_CB_MAX_GROUPS; ++k) {
+    if (k >= groups) { a.table[k] = nullptr; a.rows[k] = 0; }
+    if (a.rows[k] > max_rows) max_rows = a.rows[k];
+  }
+  note_route("hta_cb_rolled_kernel<D=%d,rows=%d,W=%d,%s,mass=%d,U=%d,groups=%d,nodes=%d%s>", D, max_rows, W, itemsize == 4 ? "f32" : "f64",
+             mass_kind, U, groups, m->info[5], a.pre ? ",predrawn" : "");
+  profile_begin((hipStream_t)stream);
+  int rc = HTA_OK;
+  if (a.pre) rc = launch(m->predraw, "hta_jit_rolled_sample (pre-draw)", a.C * (int64_t)a.n_traj, &a, sizeof(a), (hipStream_t)stream, 256);
+  if (rc == HTA_OK) rc = launch(m->rolled, "hta_jit_rolled_sample", a.C, &a, sizeof(a), (hipStream_t)stream, 64u * W, 64, (unsigned)lds);
   profile_end((hipStream_t)stream);
   return rc;
 }

@@ -4,6 +4,8 @@ The reference's hot spot for a general target is ``params_grad`` (hamiltorch/sam
 :33-66): autograd through the user's callable, once per leapfrog step - "84 % of HMC wall time" on its own CPU path, and on a
 GPU ~38 eager launches per step around kernels that take microseconds.  This package removes the launches:
 
+  roll.py     a likelihood summed over many data rows - too large as straight-line code - is ROLLED: one term function, a table
+              of per-row constants, a loop split over the waves of a workgroup (``csrc/jit/rolled_callback.hip.in``);
   trace.py    the callable is traced ONCE per target (torch.fx ``make_fx``) and lowered element by element to a scalar graph;
   ir.py       reverse-mode differentiation, simplification and common-subexpression sharing on that graph;
   emit.py     value + gradient (and, for the Riemannian samplers, Hessian + third-derivative contraction) as straight-line
@@ -128,6 +130,20 @@ class CompiledHMC:
         return self._path
 
 
+class CompiledRolled(CompiledHMC):
+    """A traced callable ROLLED over its data rows (roll.py) and compiled into the rolled trajectory kernel
+    (csrc/jit/rolled_callback.hip.in).  The generated text holds the term functions and no data: `rolled.groups[k].table` are the
+    per-row constants an engine uploads, and callables of one structure over different data share one code object."""
+
+    def __init__(self, traced, rolled, generated, dtype, mass_kind):
+        super().__init__(traced, generated, runtime.SKELETON_ROLLED, dtype, mass_kind)
+        self.rolled = rolled
+
+    def path(self):
+        raise Unsupported("a likelihood rolled over its %d data rows is compiled for sample() with plain HMC only, not for leapfrog() paths "
+                          "(straight-line code for it is beyond %d scalar operations)" % (sum(self.rolled.rows), runtime.MAX_HMC_NODES))
+
+
 class CompiledDerivs(CompiledHMC):
     """A traced callable compiled into the derivative kernels of the Riemannian samplers (csrc/jit/derivs_callback.hip.in)."""
 
@@ -178,7 +194,10 @@ def _finish(out, path):
 
 def _compile(fn, example, dtype, mass_kind, fresh, path=False):
     _note("")
-    cfg = (int(example.numel()), dtype, mass_kind, example.device.type)
+    # (the rolling switches are part of the key: an entry made under one setting is not handed out under another)
+    # ('force' rolls for sample() what it keeps straight-line for leapfrog(): there the two callers do not share an entry)
+    cfg = (int(example.numel()), dtype, mass_kind, example.device.type, runtime.roll_mode(), runtime.rolled_table_mode(),
+           bool(path) and runtime.roll_mode() == "force")
     sig = objs = None
     try:
         sig, objs = _signature(fn)
@@ -196,15 +215,26 @@ def _compile(fn, example, dtype, mass_kind, fresh, path=False):
     try:
         traced = trace_callback(fn, example)
         stats["traced"] += 1
-        _check_against_autograd(traced, fn, example)
-        if mass_kind == "derivs":
-            out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype), runtime.SKELETON_DERIVS, dtype, mass_kind)
-        elif mass_kind in ("rmhmc", "rmhmc-jitter"):
-            out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype, mass_kind == "rmhmc-jitter"), runtime.SKELETON_RMHMC,
-                                 dtype, mass_kind)
+        if mass_kind in ("derivs", "rmhmc", "rmhmc-jitter"):
+            _too_large_unrolled(traced, runtime.MAX_DERIV_NODES, "the derivative and RMHMC kernels")
+            _check_against_autograd(traced, fn, example)
+            if mass_kind == "derivs":
+                out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype), runtime.SKELETON_DERIVS, dtype, mass_kind)
+            else:
+                out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype, mass_kind == "rmhmc-jitter"), runtime.SKELETON_RMHMC,
+                                     dtype, mass_kind)
         else:
-            out = CompiledHMC(traced, runtime.hmc_generated_source(traced, dtype, mass_kind), runtime.SKELETON_HMC, dtype, mass_kind)
-        ret = _finish(out, path)
+            out = _hmc_or_rolled(traced, fn, example, dtype, mass_kind, path)
+        try:
+            ret = _finish(out, path)
+        except Unsupported as e:
+            if not isinstance(out, CompiledRolled):
+                raise
+            # a leapfrog() path was asked of a callable that compiles in its rolled form only: refused with that reason, and the
+            # rolled entry is kept for sample()
+            stats["unsupported"] += 1
+            _note(str(e))
+            ret = e
     except Unsupported as e:
         stats["unsupported"] += 1
         _note(str(e))
@@ -217,7 +247,51 @@ def _compile(fn, example, dtype, mass_kind, fresh, path=False):
             pass
     if isinstance(out, Unsupported):
         raise out
+    if isinstance(ret, Unsupported):
+        raise ret
     return ret
+
+
+def _too_large_unrolled(traced, limit, who):
+    """A value graph that is beyond `limit` scalar operations on its own is refused BEFORE it is differentiated (the derivatives of
+    an unrolled likelihood over thousands of rows take seconds to build, only to be turned down for their size)."""
+    live = len(traced.graph.reachable([traced.value]))
+    if live > limit:
+        raise Unsupported("the value alone is %d scalar operations (limit %d with its derivatives); likelihoods rolled over their data rows "
+                          "are compiled for a single callable under plain HMC in sample(), not for %s" % (live, limit, who))
+
+
+def _hmc_or_rolled(traced, fn, example, dtype, mass_kind, path):
+    """The straight-line trajectory kernel's entry for a traced callable - or, where HAMILTORCH_AMD_JIT_ROLL allows it, the rolled
+    one (roll.py).  'auto' rolls only what the straight-line route refuses FOR ITS SIZE, and looks at the value graph's own size
+    first so that the gradient of an unrolled likelihood is not built just to be thrown away; everything that compiled before keeps
+    its text.  'force' rolls whenever a group exists (leapfrog() paths excepted: they have no rolled form)."""
+    mode = runtime.roll_mode()
+    big = len(traced.graph.reachable([traced.value])) > runtime.MAX_HMC_NODES
+    if (mode == "auto" and big) or (mode == "force" and (big or not path)):
+        try:
+            return _rolled(traced, fn, example, dtype, mass_kind)
+        except Unsupported as e:
+            if big:
+                raise Unsupported("the value is %d scalar operations (limit %d for straight-line code) and it does not roll: %s"
+                                  % (len(traced.graph.reachable([traced.value])), runtime.MAX_HMC_NODES, e)) from None
+            _note("not rolled: %s" % e)      # 'force' on a callable that fits straight-line code: that route, the reason kept until it compiles
+    _check_against_autograd(traced, fn, example)
+    try:
+        return CompiledHMC(traced, runtime.hmc_generated_source(traced, dtype, mass_kind), runtime.SKELETON_HMC, dtype, mass_kind)
+    except Unsupported as e:
+        if mode != "auto" or "scalar operations (limit" not in str(e) or traced.D > runtime.MAX_HMC_DIM:
+            raise
+        try:
+            return _rolled(traced, fn, example, dtype, mass_kind)
+        except Unsupported as e2:
+            raise Unsupported("%s and it does not roll: %s" % (e, e2)) from None
+
+
+def _rolled(traced, fn, example, dtype, mass_kind):
+    rolled = runtime.rolled_program(traced)
+    _check_against_autograd(traced, fn, example, evaluate=lambda pts: rolled.evaluate(pts, "float64"))
+    return CompiledRolled(traced, rolled, runtime.rolled_generated_source(rolled, dtype, mass_kind), dtype, mass_kind)
 
 
 def _hit(out, path):
@@ -278,6 +352,7 @@ def compile_split(fns, example, dtype, mass_kind, fresh=False, _path=False):
                     raise Unsupported("not a callable")
                 tr = trace_callback(fn, example)
                 stats["traced"] += 1
+                _too_large_unrolled(tr, runtime.MAX_SPLIT_NODES, "lists of callables under the split integrators")
                 _check_against_autograd(tr, fn, example)
             except Unsupported as e:
                 raise Unsupported("subset %d: %s" % (m, e)) from None
@@ -299,17 +374,21 @@ def compile_split(fns, example, dtype, mass_kind, fresh=False, _path=False):
     return ret
 
 
-def _check_against_autograd(traced, fn, example, points=4):
+def _check_against_autograd(traced, fn, example, points=4, evaluate=None):
     """A fresh trace is believed only after its VALUE AND GRADIENT (the graph's own reverse mode, evaluated in numpy) reproduce the callable
     under torch.autograd at a few points around the example.  The trace records operations, not autograd semantics: a `torch.no_grad()`
     block, a custom `autograd.Function` backward or a gradient hook inside the callable would compile to the derivative of what is
-    COMPUTED, not to what autograd returns - such callables are refused here (the run-time check of sample() compares values only)."""
+    COMPUTED, not to what autograd returns - such callables are refused here (the run-time check of sample() compares values only).
+    `evaluate(points[k, D]) -> [k, 1 + D]` replaces the graph's own value + gradient: the rolled program's interpreter (roll.py)."""
     import numpy as np
     g = torch.Generator(device="cpu").manual_seed(0x5EED)
     base = example.detach().double().cpu()
     pts = torch.cat([base[None], base[None] + 0.05 * (1.0 + base.abs())[None] * torch.randn(points - 1, base.numel(), generator=g, dtype=torch.float64)])
-    grads = traced.grad()
-    mine = traced.graph.evaluate([traced.value] + grads, pts.numpy(), np.float64)
+    if evaluate is None:
+        grads = traced.grad()
+        mine = traced.graph.evaluate([traced.value] + grads, pts.numpy(), np.float64)
+    else:
+        mine = evaluate(pts.numpy())
     tol = 2e-3 if example.dtype == torch.float32 else 1e-7
     for k in range(pts.shape[0]):
         x = pts[k].to(device=example.device, dtype=example.dtype).requires_grad_(True)

@@ -23,6 +23,7 @@ _HEADERS = (("cb_math.hpp", "jit/cb_math.hpp"), ("philox.hpp", "philox.hpp"), ("
 SKELETON_HMC = "jit/hmc_callback.hip.in"
 SKELETON_SPLIT = "jit/split_callback.hip.in"
 SKELETON_PATH = "jit/path_callback.hip.in"
+SKELETON_ROLLED = "jit/rolled_callback.hip.in"
 SKELETON_DERIVS = "jit/derivs_callback.hip.in"
 SKELETON_RMHMC = "jit/rmhmc_callback.hip.in"
 # (SLP vectorisation ON: the straight-line callback code packs into v_pk_mul / v_pk_fma pairs - 67 -> 59 instructions per
@@ -31,7 +32,8 @@ OPTIONS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast")
 
 _lock = threading.Lock()
 _text = {}
-_code = {}          # sha1 -> bytes (gfx950 code object)
+_code = {}          # sha1 -> bytes (gfx950 code object); the 64 most recently used
+MAX_CODE = 64
 _modules = {}       # (sha1, device index) -> Module
 stats = {"compiled": 0, "code_hits": 0, "loaded": 0, "compile_seconds": 0.0}
 
@@ -62,7 +64,9 @@ def compile_source(generated, skeleton):
         h.update(part.encode()); h.update(b"\0")
     key = h.hexdigest()
     with _lock:
-        hit = _code.get(key)
+        hit = _code.pop(key, None)
+        if hit is not None:
+            _code[key] = hit            # most recently used last
     if hit is not None:
         stats["code_hits"] += 1
         return key, hit
@@ -87,6 +91,8 @@ def compile_source(generated, skeleton):
     finally:
         lib.hta_jit_free(code)
     with _lock:
+        while len(_code) >= MAX_CODE:
+            _code.pop(next(iter(_code)))
         _code[key] = blob
     stats["compiled"] += 1
     return key, blob
@@ -191,6 +197,104 @@ def hmc_final_logp(workspace, C, D, dtype):
     """log p at the state the last launch ended in ([C] view of the workspace's second block)."""
     item = torch.empty((), dtype=dtype).element_size()
     return workspace[C * D * item:C * D * item + C * item].view(dtype)
+
+
+# ---- plain HMC on a callable rolled over its data rows (roll.py) -----------------------------------------------------------
+ROLLED_WAVES = (1, 2, 4, 8, 16)  # W: waves of one workgroup of 64 chains (csrc/jit/rolled_callback.hip.in)
+ROLLED_LDS = 64 << 10           # bytes of dynamic LDS of one workgroup at most (HTA_CB_ROLLED_LDS)
+ROLLED_TABLE_DEFAULT = "direct"
+ROLLED_MAX_WAVES_GRID = 2048    # waves of one launch that share the row loops (beyond: the chains fill the machine themselves)
+
+
+# The rolled route is OPT-IN until its rate is measured against the torch-evaluated route on the workload of tools/jit_roll_rate.py
+# (profiles/r09a_rolled.json holds no rates yet): a default must not be slower than what it replaces.  'auto' is what the default
+# becomes once those numbers exist and favour it.
+ROLL_DEFAULT = "0"
+
+
+def roll_mode():
+    """HAMILTORCH_AMD_JIT_ROLL: 'auto' (roll where the straight-line route refuses for size), '0' (never), 'force' (whenever a
+    group exists: tests at small shapes); unset: ROLL_DEFAULT."""
+    m = os.environ.get("HAMILTORCH_AMD_JIT_ROLL", ROLL_DEFAULT).strip().lower()
+    return m if m in ("0", "force", "auto") else ROLL_DEFAULT
+
+
+def rolled_table_mode():
+    """HAMILTORCH_AMD_JIT_ROLL_TABLE: how the row loop reads a group's table - 'direct' (wave-uniform loads from global memory) or
+    'lds' (a tile of rows per wave staged through LDS); csrc/jit/rolled_callback.hip.in.  The default is the faster of the two on the
+    workload of tools/jit_roll_rate.py."""
+    m = os.environ.get("HAMILTORCH_AMD_JIT_ROLL_TABLE", ROLLED_TABLE_DEFAULT).strip().lower()
+    return m if m in ("direct", "lds") else ROLLED_TABLE_DEFAULT
+
+
+def rolled_max_waves(D, itemsize, live=0):
+    """The waves per workgroup the rolled kernel is BUILT for (its launch bound): every wave holds theta, p, the gradient, the
+    pre-drawn record and the partial sums in registers next to the term's temporaries, and a workgroup of 16 / 8 / 4 waves leaves a
+    lane 128 / 256 / 512 registers (4 waves: what the straight-line kernel has).  `live`: the live operations of the largest term
+    with its gradient.  Logistic / Gaussian terms (20 - 60 operations) take 64 + 6 D registers in float32 and 110 + 10 D in float64
+    (double-precision log and exp): no scratch within the first bounds below, tests/test_jit_roll_cpu.py.  A heavier term gets the
+    wider register budget instead of more waves - a heuristic: beyond it the compiler spills, which is slower and not wrong."""
+    if itemsize == 4:
+        return 16 if (D <= 10 and live <= 80) else (8 if (D <= 30 and live <= 250) else 4)
+    return 8 if (D <= 12 and live <= 120) else 4
+
+
+def rolled_waves(C, D, U, max_rows, itemsize, live=0):
+    """THE rule for W: the largest of ROLLED_WAVES for which the partial sums fit the LDS bound (W * 64 * (1 + D + U) * itemsize <=
+    64 KB), every wave has at least 8 rows of the largest group (W <= rows / 8), the launch has at most 2048 waves
+    (ceil(C / 64) * W) and the kernel's launch bound holds (rolled_max_waves)."""
+    blocks = -(-int(C) // 64)
+    best = 1
+    for W in ROLLED_WAVES:
+        if (W * 64 * (1 + D + U) * itemsize <= ROLLED_LDS and W * 8 <= max_rows and blocks * W <= ROLLED_MAX_WAVES_GRID
+                and W <= rolled_max_waves(D, itemsize, live)):
+            best = W
+    return best
+
+
+def rolled_program(traced):
+    """roll.Rolled of a traced callable under the limits of the rolled kernel; raises Unsupported with the reason."""
+    from . import roll
+    if traced.D > MAX_HMC_DIM:
+        raise Unsupported("D = %d: the chain-per-lane kernel holds theta, p and the gradient in registers (D <= %d)" % (traced.D, MAX_HMC_DIM))
+    return roll.roll(traced.graph, traced.value, MAX_HMC_NODES)
+
+
+def rolled_generated_source(rolled, dtype, mass_kind):
+    """The generated include of csrc/jit/rolled_callback.hip.in for a roll.Rolled program."""
+    item = torch.empty((), dtype=dtype).element_size()
+    live = max(g.live for g in rolled.groups)
+    return emit.rolled_value_grad_source(rolled, dtype_name(dtype), mass_kind, rolled_max_waves(rolled.D, item, live),
+                                         rolled_table_mode() == "lds")
+
+
+def rolled_sample(module, cur, init, U, tables, rows, waves, mass_kind, inv_mass, mass_factor, L, eps, n_traj, traj_offset, burn, seed,
+                  chain_offset, samples, reject_count, workspace, H_old=None, H_new=None, accept=None, resume=False, pre=None):
+    """hta_jit_rolled_sample: trajectories [traj_offset, traj_offset + n_traj) on the rolled callback, one launch; `tables` are the
+    groups' device tables ([rows, slots] in the run's dtype), `waves` the waves per workgroup of 64 chains."""
+    _abi.require_device(cur, "params")
+    C, D = cur.shape
+    a = _abi.HtaCbRolledArgs()
+    a.cur, a.init = cur.data_ptr(), _abi._p(init, cur).value
+    a.inv_mass = None if inv_mass is None else _abi._p(inv_mass, cur).value
+    a.mass_factor = None if mass_factor is None else _abi._p(mass_factor, cur).value
+    a.samples = None if samples is None else _abi._p(samples, cur).value
+    a.reject_count = reject_count.data_ptr()
+    a.H_old = None if H_old is None else _abi._p(H_old, cur).value
+    a.H_new = None if H_new is None else _abi._p(H_new, cur).value
+    a.accept = None if accept is None else accept.data_ptr()
+    a.C, a.eps, a.seed, a.chain_offset = C, float(eps), int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_offset)
+    a.L, a.n_traj, a.traj_offset, a.burn = int(L), int(n_traj), int(traj_offset), int(burn)
+    a.resume = 1 if resume else 0
+    if pre is not None:
+        a.pre, a.pre_bytes = pre.data_ptr(), pre.numel() * pre.element_size()
+    for k, (t, r) in enumerate(zip(tables, rows)):
+        a.table[k], a.rows[k] = _abi._p(t, cur).value, int(r)
+    a.waves = int(waves)
+    with torch.cuda.device(cur.device):
+        _abi._check(_abi.load().hta_jit_rolled_sample(module.handle, ctypes.byref(a), D, int(U), len(tables), cur.element_size(),
+                                                      int(mass_kind), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                                      _abi._stream(cur)), "hta_jit_rolled_sample")
 
 
 # ---- split HMC on a list of callables ---------------------------------------------------------------------------------

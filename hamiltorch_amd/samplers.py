@@ -865,7 +865,8 @@ def _compiled_engine(log_prob_func, theta0, inv_mass, fresh=False):
     except jit.Unsupported as e:
         _abi.load().hta_jit_note_fallback(str(e)[:140].encode("utf-8", "replace"))
         return None
-    return _CompiledHMC(log_prob_func, comp, reused=jit.stats["trace_hits"] > before)
+    cls = _CompiledRolledHMC if isinstance(comp, jit.CompiledRolled) else _CompiledHMC
+    return cls(log_prob_func, comp, reused=jit.stats["trace_hits"] > before)
 
 
 class _CompiledHMC(_Engine):
@@ -906,12 +907,15 @@ class _CompiledHMC(_Engine):
                 self._pre = torch.empty(need, dtype=torch.uint8, device=self.cur.device)
         for start in range(n0, n0 + count, chunk):
             k = min(chunk, n0 + count - start)
-            runtime.hmc_sample(self.module, self.cur, self.theta0, self.kind, self.im, self.mf, L, eps, k, start, self.burn,
-                               self.seed, self.off, self.samples, self.rejected, self.ws, H_old, H_new, resume=self._ran,
-                               pre=self._pre if self._predraw else None)
+            self._launch(L, eps, k, start, H_old, H_new, self._pre if self._predraw else None)
             self._ran = True
             if progress is not None:
                 progress.update(min(self.N, start + k) - 1)
+
+    def _launch(self, L, eps, k, start, H_old, H_new, pre):
+        from .jit import runtime
+        runtime.hmc_sample(self.module, self.cur, self.theta0, self.kind, self.im, self.mf, L, eps, k, start, self.burn,
+                           self.seed, self.off, self.samples, self.rejected, self.ws, H_old, H_new, resume=self._ran, pre=pre)
 
     def verify(self, k=128):
         """log p of the states the run ended in: the kernel's own value against the callable evaluated by torch (one vmap call on up
@@ -927,6 +931,31 @@ class _CompiledHMC(_Engine):
         tol = (2e-4 if mine.dtype == torch.float32 else 1e-9)
         close = (mine - ref).abs() <= tol * (10.0 + ref.abs())
         return bool(((fin_a == fin_b) & (close | ~fin_b)).all())
+
+
+class _CompiledRolledHMC(_CompiledHMC):
+    """A likelihood summed over data rows, rolled (hamiltorch_amd/jit/roll.py) and compiled into the rolled trajectory kernel
+    (csrc/jit/rolled_callback.hip.in): the trajectory loop of _CompiledHMC's kernel, the rows' constants in device tables, the row
+    loop divided over the W waves of a workgroup of 64 chains.  Chunking, pre-drawn records and verify() are _CompiledHMC's."""
+
+    WAVES = None        # tests: a fixed W instead of the rule (jit.runtime.rolled_waves)
+
+    def begin(self, theta0, N, burn, inv_mass, seed, chain_offset):
+        from .jit import runtime
+        super().begin(theta0, N, burn, inv_mass, seed, chain_offset)
+        C, D = theta0.shape
+        r = self.comp.rolled
+        # (a group whose constants are all literals has no slot: its table is one unused element, the pointer stays valid)
+        self.tables = [torch.as_tensor(g.table if g.slots else [[0.0]], dtype=theta0.dtype).contiguous().to(theta0.device)
+                       for g in r.groups]
+        self.waves = self.WAVES or runtime.rolled_waves(C, D, r.U, max(r.rows), theta0.element_size(), max(g.live for g in r.groups))
+
+    def _launch(self, L, eps, k, start, H_old, H_new, pre):
+        from .jit import runtime
+        r = self.comp.rolled
+        runtime.rolled_sample(self.module, self.cur, self.theta0, r.U, self.tables, r.rows, self.waves, self.kind, self.im, self.mf,
+                              L, eps, k, start, self.burn, self.seed, self.off, self.samples, self.rejected, self.ws, H_old, H_new,
+                              resume=self._ran, pre=pre)
 
 
 _SPLIT_KIND_OF = {Integrator.SPLITTING: _abi.SPLIT_SYMMETRIC, Integrator.SPLITTING_RAND: _abi.SPLIT_RAND,

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HTA_ABI_VERSION 13
+#define HTA_ABI_VERSION 14
 
 #define HTA_OK 0
 #define HTA_ERR_INVALID (-1)   /* bad argument                           */
@@ -448,6 +448,16 @@ int hta_net_forward_f64(const double* theta, int64_t S, int n_layers, const int*
  *                     (split_permutation(seed, 0, M), one order per call).  The arguments are checked first, steps == 0 then
  *                     returns HTA_OK without a launch; D / M / itemsize / mass_kind must be the module's (else
  *                     HTA_ERR_INVALID, nothing is launched).  No workspace.
+ *   hta_jit_rolled_sample  (ABI 14) plain HMC like hta_jit_hmc_sample on a callable that was ROLLED over its data rows
+ *                     (hamiltorch_amd/jit/roll.py: a likelihood summed over a data set as one term function, per-row constants in
+ *                     tables, a loop): csrc/jit/rolled_callback.hip.in, a module of its own (kernel set HTA_CB_SET_ROLLED; info[6] = U
+ *                     uniforms, info[7] = groups).  HtaCbRolledArgs = the fields of HtaCbHmcArgs + `table[k]` (device, [rows[k], slots]
+ *                     in the run's dtype), `rows[k]`, `waves`: a workgroup is 64 chains x `waves` waves (1, 2, 4, 8 or 16), every
+ *                     wave integrates the same chains, the rows are divided over the waves and their partial sums are added in wave
+ *                     order through waves x 64 x (1 + D + U) x itemsize bytes of LDS (<= 64 KB).  Workspace and pre-draw buffer as for
+ *                     hta_jit_hmc_sample.  A wave count outside the set, a NULL table, rows <= 0 or an LDS request beyond the bound
+ *                     return HTA_ERR_INVALID before the module is looked at; D / U / groups / itemsize / mass_kind must be the
+ *                     module's; nothing is launched otherwise.
  *   hta_jit_derivs    which = 0: logp[C], grad[C,D], neg_hess[C,D,D] (each optional) at theta[C,D]; which = 1:
  *                     contract[C,D] = d_k < Hess log p, M > with M[C,D,D] held fixed.
  *   hta_jit_note_fallback  records in hta_last_route() WHY a callable was not compiled (the caller then runs the pieces path).
@@ -469,6 +479,8 @@ int64_t hta_jit_hmc_workspace_bytes(int64_t C, int D, int itemsize);
 int64_t hta_jit_hmc_predraw_bytes(int64_t C, int D, int n_traj, int itemsize);
 int hta_jit_hmc_sample(void* module, const HtaCbHmcArgs* args, int D, int itemsize, int mass_kind, void* workspace,
                        int64_t workspace_bytes, void* stream);
+int hta_jit_rolled_sample(void* module, const HtaCbRolledArgs* args, int D, int U, int groups, int itemsize, int mass_kind,
+                          void* workspace, int64_t workspace_bytes, void* stream);
 int64_t hta_jit_split_workspace_bytes(int64_t C, int D, int itemsize);
 int hta_jit_split_sample(void* module, const HtaCbHmcArgs* args, int D, int M, int itemsize, int mass_kind, int split_kind,
                          void* workspace, int64_t workspace_bytes, void* stream);
