@@ -24,54 +24,54 @@
 #define HTA_CB_SPLIT_RAND 1
 #define HTA_CB_SPLIT_KMID 2
 
-typedef struct HtaCbHmcArgs {
-  void* cur;               /* [C, D] current state, in / out                                                    */
-  const void* init;        /* [C, D] params_init (the reference's Q2 reset, samplers.py:1018)                   */
-  const void* inv_mass;    /* (D,) | (D,D) | NULL                                                               */
-  const void* mass_factor; /* sqrt(mass) (D,) | chol(mass) (D,D) lower, row-major | NULL                        */
-  void* samples;           /* [S, C, D] or NULL                                                                 */
-  int* reject_count;       /* [C]                                                                               */
-  void* H_old;             /* [C] of the launch's LAST trajectory, or NULL                                      */
-  void* H_new;             /* [C] ditto                                                                         */
-  unsigned char* accept;   /* [C] ditto                                                                         */
-  void* gcur;              /* [C, D] workspace: gradient at the current state (NULL for hta_cb_split_kernel)    */
-  void* lp_out;            /* [C] log p at the state the launch ended in (checked against the callback), or NULL */
-  long long C;
-  double eps;
-  unsigned long long seed, chain_offset;
-  int L, n_traj, traj_offset, burn;
-  int resume;              /* 1: (log p, gradient) at `cur` are in the workspace from the previous launch of this run */
-  int split_kind;          /* hta_cb_split_kernel: HTA_CB_SPLIT_*; 0 elsewhere                                                */
-  void* pre;               /* NULL, or [n_traj, D + 1, C] pre-drawn records of this launch (momentum after the mass factor, log u):
-                              filled by hta_cb_predraw_kernel in front of the trajectory kernel (hta_jit_hmc_predraw_bytes)       */
+/* The fields of a trajectory launch on compiled callables: HtaCbHmcArgs is this list, HtaCbRolledArgs starts with it.  ONE list, so that
+ * the two cannot drift apart; the names stay flat (a.cur, a.pre) in C and in hamiltorch_amd/_abi.py. */
+#define HTA_CB_HMC_FIELDS                                                                                                          \
+  void* cur;               /* [C, D] current state, in / out                                                    */                 \
+  const void* init;        /* [C, D] params_init (the reference's Q2 reset, samplers.py:1018)                   */                 \
+  const void* inv_mass;    /* (D,) | (D,D) | NULL                                                               */                 \
+  const void* mass_factor; /* sqrt(mass) (D,) | chol(mass) (D,D) lower, row-major | NULL                        */                 \
+  void* samples;           /* [S, C, D] or NULL                                                                 */                 \
+  int* reject_count;       /* [C]                                                                               */                 \
+  void* H_old;             /* [C] of the launch's LAST trajectory, or NULL                                      */                 \
+  void* H_new;             /* [C] ditto                                                                         */                 \
+  unsigned char* accept;   /* [C] ditto                                                                         */                 \
+  void* gcur;              /* [C, D] workspace: gradient at the current state (NULL for hta_cb_split_kernel)    */                 \
+  void* lp_out;            /* [C] log p at the state the launch ended in (checked against the callback), or NULL */                \
+  long long C;                                                                                                                     \
+  double eps;                                                                                                                      \
+  unsigned long long seed, chain_offset;                                                                                           \
+  int L, n_traj, traj_offset, burn;                                                                                                \
+  int resume;              /* 1: (log p, gradient) at `cur` are in the workspace from the previous launch of this run */           \
+  int split_kind;          /* hta_cb_split_kernel: HTA_CB_SPLIT_*; 0 elsewhere                                  */                 \
+  void* pre;               /* NULL, or [n_traj, D + 1, C] pre-drawn records of this launch (momentum after the mass factor, log u): \
+                              filled by hta_cb_predraw_kernel in front of the trajectory kernel (hta_jit_hmc_predraw_bytes) */      \
   long long pre_bytes;
+
+typedef struct HtaCbHmcArgs {
+  HTA_CB_HMC_FIELDS
 } HtaCbHmcArgs;
 
-/* hta_jit_rolled_sample (csrc/jit/rolled_callback.hip.in): the fields of HtaCbHmcArgs, in their order, then the groups' tables */
+/* hta_jit_rolled_sample (csrc/jit/rolled_callback.hip.in): the fields of HtaCbHmcArgs, then the groups' tables */
 typedef struct HtaCbRolledArgs {
-  void* cur;
-  const void* init;
-  const void* inv_mass;
-  const void* mass_factor;
-  void* samples;
-  int* reject_count;
-  void* H_old;
-  void* H_new;
-  unsigned char* accept;
-  void* gcur;
-  void* lp_out;
-  long long C;
-  double eps;
-  unsigned long long seed, chain_offset;
-  int L, n_traj, traj_offset, burn;
-  int resume;
-  int split_kind;          /* 0 */
-  void* pre;
-  long long pre_bytes;
+  HTA_CB_HMC_FIELDS
   const void* table[HTA_CB_MAX_GROUPS]; /* [rows[k], slots of group k] per-row constants in the run's dtype, row-major; unused groups NULL */
   int rows[HTA_CB_MAX_GROUPS];          /* rows of group k (> 0 for the module's groups)                                             */
   int waves;               /* W: waves per workgroup of 64 chains, 1 | 2 | 4 | 8 | 16; wave w takes rows [w ceil(rows / W), ...) */
 } HtaCbRolledArgs;
+
+/* the layout the kernels, the library and hamiltorch_amd/_abi.py agree on (tests/test_jit_cpu.py holds the ctypes side) */
+#ifdef __cplusplus
+#define HTA_CB_LAYOUT(cond) static_assert(cond, #cond)
+#else
+#define HTA_CB_LAYOUT(cond) _Static_assert(cond, #cond)
+#endif
+HTA_CB_LAYOUT(sizeof(HtaCbHmcArgs) == 160 && sizeof(HtaCbRolledArgs) == 216);
+HTA_CB_LAYOUT(__builtin_offsetof(HtaCbHmcArgs, pre) == 144 && __builtin_offsetof(HtaCbHmcArgs, pre_bytes) == 152);
+HTA_CB_LAYOUT(__builtin_offsetof(HtaCbRolledArgs, pre) == 144 && __builtin_offsetof(HtaCbRolledArgs, pre_bytes) == 152);
+HTA_CB_LAYOUT(__builtin_offsetof(HtaCbRolledArgs, table) == 160 && __builtin_offsetof(HtaCbRolledArgs, rows) == 192 &&
+              __builtin_offsetof(HtaCbRolledArgs, waves) == 208);
+#undef HTA_CB_LAYOUT
 
 typedef struct HtaCbRmhmcArgs {
   void* cur;             /* [C, D] current state, in / out                                     */

@@ -100,6 +100,69 @@ int launch(hipFunction_t fn, const char* who, int64_t C, void* args, size_t byte
   return HTA_OK;
 }
 
+// which kernels a module of each kernel set (hta_cb_info[4]) exports, and where hta_jit_load keeps them
+const struct KernelSet {
+  int set;
+  const char* name;
+  hipFunction_t Module::*fn;
+  const char* name2;          // a second kernel of the set, or NULL
+  hipFunction_t Module::*fn2;
+} kKernelSets[] = {
+    {HTA_CB_SET_HMC, "hta_cb_hmc_kernel", &Module::hmc, "hta_cb_predraw_kernel", &Module::predraw},
+    {HTA_CB_SET_DERIVS, "hta_cb_derivs_kernel", &Module::derivs, "hta_cb_contract_kernel", &Module::contract},
+    {HTA_CB_SET_RMHMC, "hta_cb_rmhmc_kernel", &Module::rmhmc, nullptr, nullptr},
+    {HTA_CB_SET_SPLIT, "hta_cb_split_kernel", &Module::split, nullptr, nullptr},
+    {HTA_CB_SET_PATH, "hta_cb_path_kernel", &Module::path, nullptr, nullptr},          // a list (info[6] = M > 0): hta_cb_split_path_kernel
+    {HTA_CB_SET_ROLLED, "hta_cb_rolled_kernel", &Module::rolled, "hta_cb_predraw_kernel", &Module::predraw},
+};
+
+const char* dtype_name(int itemsize) { return itemsize == 4 ? "f32" : "f64"; }
+const char* split_name(int kind) { return kind == HTA_CB_SPLIT_RAND ? "rand" : kind == HTA_CB_SPLIT_KMID ? "kmid" : "symmetric"; }
+
+// What hta_jit_hmc_sample, hta_jit_rolled_sample and hta_jit_split_sample ask of their argument block (HtaCbHmcArgs or
+// HtaCbRolledArgs) before anything is launched, in three parts so that each entry point keeps the order of its checks; `who` is the
+// entry point's name, `need` / `need_name` the function that sizes its workspace.
+template <typename Args>
+int check_args(const char* who, const Args* args, int D, int itemsize) {
+  HTA_REQUIRE(args && args->cur && args->init && args->reject_count && args->C > 0 && args->L >= 0 && args->n_traj >= 0 && D > 0 &&
+                  (itemsize == 4 || itemsize == 8),
+              "%s: bad arguments", who);
+  return HTA_OK;
+}
+
+template <typename Args>
+int check_mass(const char* who, const Args* args, int mass_kind) {
+  HTA_REQUIRE(mass_kind == HTA_MASS_NONE || (args->inv_mass && args->mass_factor), "%s: mass operands are NULL", who);
+  return HTA_OK;
+}
+
+template <typename Args>
+int check_buffers(const char* who, const Args* args, int D, int itemsize, const void* workspace, int64_t workspace_bytes,
+                  int64_t (*need)(int64_t, int, int), const char* need_name) {
+  HTA_REQUIRE(workspace && workspace_bytes >= need(args->C, D, itemsize), "%s: workspace of %lld bytes, %lld needed (%s)", who,
+              (long long)workspace_bytes, (long long)need(args->C, D, itemsize), need_name);
+  const int64_t pre_need = hta_jit_hmc_predraw_bytes(args->C, D, args->n_traj, itemsize);
+  HTA_REQUIRE(!args->pre || args->pre_bytes >= pre_need, "%s: pre-draw buffer of %lld bytes, %lld needed (hta_jit_hmc_predraw_bytes)", who,
+              (long long)args->pre_bytes, (long long)pre_need);
+  return HTA_OK;
+}
+
+// Places the carried values in the workspace - gcur[C, D] (plain HMC: carry_grad) then lp_out[C] - and enqueues the launch: the
+// pre-draw kernel (named `who_pre` in a launch error) when the block has a record buffer, then `kernel` with `block` threads per 64 chains.
+template <typename Args>
+int run_sample(const char* who, const char* who_pre, const Module* m, hipFunction_t kernel, Args& a, int D, int itemsize, bool carry_grad, void* workspace,
+               hipStream_t s, unsigned block = 64, unsigned lds = 0) {
+  a.resume = a.resume ? 1 : 0;
+  a.gcur = carry_grad ? workspace : nullptr;
+  a.lp_out = carry_grad ? (char*)workspace + a.C * D * itemsize : workspace;
+  profile_begin(s);
+  int rc = HTA_OK;
+  if (a.pre) rc = launch(m->predraw, who_pre, a.C * (int64_t)a.n_traj, &a, sizeof(a), s, 256);
+  if (rc == HTA_OK) rc = launch(kernel, who, a.C, &a, sizeof(a), s, block, 64, lds);
+  profile_end(s);
+  return rc;
+}
+
 }  // namespace
 }  // namespace hta
 
@@ -185,24 +248,15 @@ int hta_jit_load(const void* code, int64_t bytes, void** module_out) {
     delete m;
     return HTA_ERR_INVALID;
   }
-  if (m->info[4] == HTA_CB_SET_HMC) {
-    e = hipModuleGetFunction(&m->hmc, m->mod, "hta_cb_hmc_kernel");
-    if (e == hipSuccess) e = hipModuleGetFunction(&m->predraw, m->mod, "hta_cb_predraw_kernel");
-  } else if (m->info[4] == HTA_CB_SET_DERIVS) {
-    e = hipModuleGetFunction(&m->derivs, m->mod, "hta_cb_derivs_kernel");
-    if (e == hipSuccess) e = hipModuleGetFunction(&m->contract, m->mod, "hta_cb_contract_kernel");
-  } else if (m->info[4] == HTA_CB_SET_RMHMC) {
-    e = hipModuleGetFunction(&m->rmhmc, m->mod, "hta_cb_rmhmc_kernel");
-  } else if (m->info[4] == HTA_CB_SET_SPLIT) {
-    e = hipModuleGetFunction(&m->split, m->mod, "hta_cb_split_kernel");
-  } else if (m->info[4] == HTA_CB_SET_ROLLED) {
-    e = hipModuleGetFunction(&m->rolled, m->mod, "hta_cb_rolled_kernel");
-    if (e == hipSuccess) e = hipModuleGetFunction(&m->predraw, m->mod, "hta_cb_predraw_kernel");
-    if (e == hipSuccess) e = hipFuncGetAttribute(&m->rolled_max_threads, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, m->rolled);
-  } else if (m->info[4] == HTA_CB_SET_PATH) {
-    e = hipModuleGetFunction(&m->path, m->mod, m->info[6] > 0 ? "hta_cb_split_path_kernel" : "hta_cb_path_kernel");
-  } else {
-    e = hipErrorInvalidValue;
+  e = hipErrorInvalidValue;
+  for (const KernelSet& k : kKernelSets) {
+    if (k.set != m->info[4]) continue;
+    const bool list_path = k.set == HTA_CB_SET_PATH && m->info[6] > 0;
+    e = hipModuleGetFunction(&(m->*k.fn), m->mod, list_path ? "hta_cb_split_path_kernel" : k.name);
+    if (e == hipSuccess && k.name2) e = hipModuleGetFunction(&(m->*k.fn2), m->mod, k.name2);
+    if (e == hipSuccess && k.set == HTA_CB_SET_ROLLED)
+      e = hipFuncGetAttribute(&m->rolled_max_threads, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, m->rolled);
+    break;
   }
   if (e != hipSuccess) {
     set_error("hta_jit_load: kernel set %d: %s", m->info[4], hipGetErrorString(e));
@@ -244,29 +298,16 @@ int hta_jit_hmc_sample(void* module, const HtaCbHmcArgs* args, int D, int itemsi
   using namespace hta;
   Module* m = (Module*)module;
   if (int rc = check_module(m, "hta_jit_hmc_sample", D, itemsize, mass_kind, HTA_CB_SET_HMC)) return rc;
-  HTA_REQUIRE(args && args->cur && args->init && args->reject_count && args->C > 0 && args->L >= 0 && args->n_traj >= 0,
-              "hta_jit_hmc_sample: bad arguments");
-  HTA_REQUIRE(mass_kind == HTA_MASS_NONE || (args->inv_mass && args->mass_factor), "hta_jit_hmc_sample: mass operands are NULL");
-  HTA_REQUIRE(workspace && workspace_bytes >= hta_jit_hmc_workspace_bytes(args->C, D, itemsize),
-              "hta_jit_hmc_sample: workspace of %lld bytes, %lld needed (hta_jit_hmc_workspace_bytes)", (long long)workspace_bytes,
-              (long long)hta_jit_hmc_workspace_bytes(args->C, D, itemsize));
-  HTA_REQUIRE(!args->pre || args->pre_bytes >= hta_jit_hmc_predraw_bytes(args->C, D, args->n_traj, itemsize),
-              "hta_jit_hmc_sample: pre-draw buffer of %lld bytes, %lld needed (hta_jit_hmc_predraw_bytes)", (long long)args->pre_bytes,
-              (long long)hta_jit_hmc_predraw_bytes(args->C, D, args->n_traj, itemsize));
+  if (int rc = check_args("hta_jit_hmc_sample", args, D, itemsize)) return rc;
+  if (int rc = check_mass("hta_jit_hmc_sample", args, mass_kind)) return rc;
+  if (int rc = check_buffers("hta_jit_hmc_sample", args, D, itemsize, workspace, workspace_bytes, hta_jit_hmc_workspace_bytes,
+                             "hta_jit_hmc_workspace_bytes"))
+    return rc;
   if (args->n_traj == 0) return HTA_OK;
   HtaCbHmcArgs a = *args;
-  a.resume = args->resume ? 1 : 0;
   a.split_kind = 0;
-  a.gcur = workspace;
-  a.lp_out = (char*)workspace + args->C * D * itemsize;
-  note_route("hta_cb_hmc_kernel<D=%d,%s,mass=%d,nodes=%d%s>", D, itemsize == 4 ? "f32" : "f64", mass_kind, m->info[5],
-             a.pre ? ",predrawn" : "");
-  profile_begin((hipStream_t)stream);
-  int rc = HTA_OK;
-  if (a.pre) rc = launch(m->predraw, "hta_jit_hmc_sample (pre-draw)", a.C * (int64_t)a.n_traj, &a, sizeof(a), (hipStream_t)stream, 256);
-  if (rc == HTA_OK) rc = launch(m->hmc, "hta_jit_hmc_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
-  profile_end((hipStream_t)stream);
-  return rc;
+  note_route("hta_cb_hmc_kernel<D=%d,%s,mass=%d,nodes=%d%s>", D, dtype_name(itemsize), mass_kind, m->info[5], a.pre ? ",predrawn" : "");
+  return run_sample("hta_jit_hmc_sample", "hta_jit_hmc_sample (pre-draw)", m, m->hmc, a, D, itemsize, true, workspace, (hipStream_t)stream);
 }
 
 /* Plain HMC on a callable ROLLED over its data rows (csrc/jit/rolled_callback.hip.in): a workgroup is 64 chains x args->waves waves,
@@ -276,9 +317,7 @@ int hta_jit_rolled_sample(void* module, const HtaCbRolledArgs* args, int D, int 
                           void* workspace, int64_t workspace_bytes, void* stream) {
   using namespace hta;
   Module* m = (Module*)module;
-  HTA_REQUIRE(args && args->cur && args->init && args->reject_count && args->C > 0 && args->L >= 0 && args->n_traj >= 0 && D > 0 &&
-                  (itemsize == 4 || itemsize == 8),
-              "hta_jit_rolled_sample: bad arguments");
+  if (int rc = check_args("hta_jit_rolled_sample", args, D, itemsize)) return rc;
   HTA_REQUIRE(U >= 0 && groups >= 1 && groups <= HTA_CB_MAX_GROUPS, "hta_jit_rolled_sample: %d groups (1 .. %d), %d uniforms", groups,
               HTA_CB_MAX_GROUPS, U);
   const int W = args->waves;
@@ -290,37 +329,26 @@ int hta_jit_rolled_sample(void* module, const HtaCbRolledArgs* args, int D, int 
   const int64_t lds = (int64_t)W * 64 * (1 + D + U) * itemsize;
   HTA_REQUIRE(lds <= HTA_CB_ROLLED_LDS, "hta_jit_rolled_sample: %d waves x 64 lanes x (1 + %d + %d) values of %d bytes = %lld bytes of LDS (limit %d)",
               W, D, U, itemsize, (long long)lds, HTA_CB_ROLLED_LDS);
-  HTA_REQUIRE(mass_kind == HTA_MASS_NONE || (args->inv_mass && args->mass_factor), "hta_jit_rolled_sample: mass operands are NULL");
+  if (int rc = check_mass("hta_jit_rolled_sample", args, mass_kind)) return rc;
   if (int rc = check_module(m, "hta_jit_rolled_sample", D, itemsize, mass_kind, HTA_CB_SET_ROLLED)) return rc;
   HTA_REQUIRE(m->info[6] == U && m->info[7] == groups, "hta_jit_rolled_sample: the module was compiled for %d uniforms and %d groups, the call has %d and %d",
               m->info[6], m->info[7], U, groups);
   HTA_REQUIRE(W * 64 <= m->rolled_max_threads, "hta_jit_rolled_sample: %d waves per workgroup, the kernel was built for %d", W,
               m->rolled_max_threads / 64);
-  HTA_REQUIRE(workspace && workspace_bytes >= hta_jit_hmc_workspace_bytes(args->C, D, itemsize),
-              "hta_jit_rolled_sample: workspace of %lld bytes, %lld needed (hta_jit_hmc_workspace_bytes)", (long long)workspace_bytes,
-              (long long)hta_jit_hmc_workspace_bytes(args->C, D, itemsize));
-  HTA_REQUIRE(!args->pre || args->pre_bytes >= hta_jit_hmc_predraw_bytes(args->C, D, args->n_traj, itemsize),
-              "hta_jit_rolled_sample: pre-draw buffer of %lld bytes, %lld needed (hta_jit_hmc_predraw_bytes)", (long long)args->pre_bytes,
-              (long long)hta_jit_hmc_predraw_bytes(args->C, D, args->n_traj, itemsize));
+  if (int rc = check_buffers("hta_jit_rolled_sample", args, D, itemsize, workspace, workspace_bytes, hta_jit_hmc_workspace_bytes,
+                             "hta_jit_hmc_workspace_bytes"))
+    return rc;
   if (args->n_traj == 0) return HTA_OK;
   HtaCbRolledArgs a = *args;
-  a.resume = args->resume ? 1 : 0;
   a.split_kind = 0;
-  a.gcur = workspace;
-  a.lp_out = (char*)workspace + args->C * D * itemsize;
   int max_rows = 0;
   for (int k = 0; k < HTA_CB_MAX_GROUPS; ++k) {
     if (k >= groups) { a.table[k] = nullptr; a.rows[k] = 0; }
     if (a.rows[k] > max_rows) max_rows = a.rows[k];
   }
-  note_route("hta_cb_rolled_kernel<D=%d,rows=%d,W=%d,%s,mass=%d,U=%d,groups=%d,nodes=%d%s>", D, max_rows, W, itemsize == 4 ? "f32" : "f64",
-             mass_kind, U, groups, m->info[5], a.pre ? ",predrawn" : "");
-  profile_begin((hipStream_t)stream);
-  int rc = HTA_OK;
-  if (a.pre) rc = launch(m->predraw, "hta_jit_rolled_sample (pre-draw)", a.C * (int64_t)a.n_traj, &a, sizeof(a), (hipStream_t)stream, 256);
-  if (rc == HTA_OK) rc = launch(m->rolled, "hta_jit_rolled_sample", a.C, &a, sizeof(a), (hipStream_t)stream, 64u * W, 64, (unsigned)lds);
-  profile_end((hipStream_t)stream);
-  return rc;
+  note_route("hta_cb_rolled_kernel<D=%d,rows=%d,W=%d,%s,mass=%d,U=%d,groups=%d,nodes=%d%s>", D, max_rows, W, dtype_name(itemsize), mass_kind, U,
+             groups, m->info[5], a.pre ? ",predrawn" : "");
+  return run_sample("hta_jit_rolled_sample", "hta_jit_rolled_sample (pre-draw)", m, m->rolled, a, D, itemsize, true, workspace, (hipStream_t)stream, 64u * W, (unsigned)lds);
 }
 
 int64_t hta_jit_split_workspace_bytes(int64_t C, int D, int itemsize) {
@@ -338,27 +366,19 @@ int hta_jit_split_sample(void* module, const HtaCbHmcArgs* args, int D, int M, i
   HTA_REQUIRE(split_kind == HTA_CB_SPLIT_SYMMETRIC || split_kind == HTA_CB_SPLIT_RAND || split_kind == HTA_CB_SPLIT_KMID,
               "hta_jit_split_sample: split kind %d", split_kind);
   HTA_REQUIRE(M >= 2 || split_kind == HTA_CB_SPLIT_RAND, "hta_jit_split_sample: the symmetric schemes need more than one subset (S:497-498)");
-  HTA_REQUIRE(args && args->cur && args->init && args->reject_count && args->C > 0 && args->L >= 0 && args->n_traj >= 0,
-              "hta_jit_split_sample: bad arguments");
-  HTA_REQUIRE(mass_kind == HTA_MASS_NONE || (args->inv_mass && args->mass_factor), "hta_jit_split_sample: mass operands are NULL");
+  if (int rc = check_args("hta_jit_split_sample", args, D, itemsize)) return rc;
+  if (int rc = check_mass("hta_jit_split_sample", args, mass_kind)) return rc;
   HTA_REQUIRE(!args->pre, "hta_jit_split_sample: pre-drawn records are not part of the split kernel");
-  HTA_REQUIRE(workspace && workspace_bytes >= hta_jit_split_workspace_bytes(args->C, D, itemsize),
-              "hta_jit_split_sample: workspace of %lld bytes, %lld needed (hta_jit_split_workspace_bytes)", (long long)workspace_bytes,
-              (long long)hta_jit_split_workspace_bytes(args->C, D, itemsize));
+  if (int rc = check_buffers("hta_jit_split_sample", args, D, itemsize, workspace, workspace_bytes, hta_jit_split_workspace_bytes,
+                             "hta_jit_split_workspace_bytes"))
+    return rc;
   if (args->n_traj == 0) return HTA_OK;
   HtaCbHmcArgs a = *args;
-  a.resume = args->resume ? 1 : 0;
   a.split_kind = split_kind;
-  a.gcur = nullptr;
-  a.pre = nullptr;
   a.pre_bytes = 0;
-  a.lp_out = workspace;
-  note_route("hta_cb_split_kernel<D=%d,M=%d,%s,mass=%d,kind=%s,nodes=%d>", D, M, itemsize == 4 ? "f32" : "f64", mass_kind,
-             split_kind == HTA_CB_SPLIT_RAND ? "rand" : split_kind == HTA_CB_SPLIT_KMID ? "kmid" : "symmetric", m->info[5]);
-  profile_begin((hipStream_t)stream);
-  const int rc = launch(m->split, "hta_jit_split_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
-  profile_end((hipStream_t)stream);
-  return rc;
+  note_route("hta_cb_split_kernel<D=%d,M=%d,%s,mass=%d,kind=%s,nodes=%d>", D, M, dtype_name(itemsize), mass_kind, split_name(split_kind),
+             m->info[5]);
+  return run_sample("hta_jit_split_sample", nullptr, m, m->split, a, D, itemsize, false, workspace, (hipStream_t)stream);
 }
 
 /* Every step of ONE leapfrog call on a compiled callable (M == 0) or a compiled list of M callables under a split integrator
@@ -388,10 +408,9 @@ int hta_jit_path_leapfrog(void* module, const HtaCbPathArgs* args, int D, int M,
   a.split_kind = M > 0 ? split_kind : 0;
   const char* mass = mass_kind == HTA_MASS_NONE ? "none" : mass_kind == HTA_MASS_DIAG ? "diag" : "full";
   if (M > 0)
-    note_route("hta_cb_split_path_kernel<D=%d,M=%d,%s,mass=%s,%s>", D, M, itemsize == 4 ? "f32" : "f64", mass,
-               split_kind == HTA_CB_SPLIT_RAND ? "rand" : split_kind == HTA_CB_SPLIT_KMID ? "kmid" : "symmetric");
+    note_route("hta_cb_split_path_kernel<D=%d,M=%d,%s,mass=%s,%s>", D, M, dtype_name(itemsize), mass, split_name(split_kind));
   else
-    note_route("hta_cb_path_kernel<D=%d,%s,mass=%s>", D, itemsize == 4 ? "f32" : "f64", mass);
+    note_route("hta_cb_path_kernel<D=%d,%s,mass=%s>", D, dtype_name(itemsize), mass);
   profile_begin((hipStream_t)stream);
   const int rc = launch(m->path, "hta_jit_path_leapfrog", a.C, &a, sizeof(a), (hipStream_t)stream);
   profile_end((hipStream_t)stream);
@@ -416,8 +435,7 @@ int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int it
   if (args->n_traj == 0) return HTA_OK;
   HtaCbRmhmcArgs a = *args;
   a.lp_out = workspace;
-  note_route("hta_cb_rmhmc_kernel<D=%d,%s,jitter=%d,nodes=%d+%d>", D, itemsize == 4 ? "f32" : "f64", has_jitter ? 1 : 0, m->info[5],
-             m->info[6]);
+  note_route("hta_cb_rmhmc_kernel<D=%d,%s,jitter=%d,nodes=%d+%d>", D, dtype_name(itemsize), has_jitter ? 1 : 0, m->info[5], m->info[6]);
   profile_begin((hipStream_t)stream);
   const int rc = launch(m->rmhmc, "hta_jit_rmhmc_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
   profile_end((hipStream_t)stream);
@@ -432,8 +450,7 @@ int hta_jit_derivs(void* module, const HtaCbDerivArgs* args, int which, int D, i
   HTA_REQUIRE(args && args->theta && args->C > 0, "hta_jit_derivs: bad arguments");
   HTA_REQUIRE(which == 0 || (args->M && (args->contract || (args->upd && args->grad_in))), "hta_jit_derivs: M / contract / upd are NULL");
   HtaCbDerivArgs a = *args;
-  note_route("%s<D=%d,%s,nodes=%d>", which ? "hta_cb_contract_kernel" : "hta_cb_derivs_kernel", D, itemsize == 4 ? "f32" : "f64",
-             m->info[5]);
+  note_route("%s<D=%d,%s,nodes=%d>", which ? "hta_cb_contract_kernel" : "hta_cb_derivs_kernel", D, dtype_name(itemsize), m->info[5]);
   return launch(which ? m->contract : m->derivs, "hta_jit_derivs", a.C, &a, sizeof(a), (hipStream_t)stream);
 }
 

@@ -19,7 +19,8 @@ from .ir import Unsupported
 
 _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 _HEADERS = (("cb_math.hpp", "jit/cb_math.hpp"), ("philox.hpp", "philox.hpp"), ("mh_rules.hpp", "mh_rules.hpp"),
-            ("jit_args.h", "jit/jit_args.h"), ("cb_hmc_shared.hpp", "jit/cb_hmc_shared.hpp"))
+            ("jit_args.h", "jit/jit_args.h"), ("cb_hmc_shared.hpp", "jit/cb_hmc_shared.hpp"),
+            ("cb_hmc_bodies.inc", "jit/cb_hmc_bodies.inc"))
 SKELETON_HMC = "jit/hmc_callback.hip.in"
 SKELETON_SPLIT = "jit/split_callback.hip.in"
 SKELETON_PATH = "jit/path_callback.hip.in"
@@ -168,12 +169,11 @@ def hmc_workspace_bytes(C, D, itemsize):
     return int(_abi.load().hta_jit_hmc_workspace_bytes(int(C), int(D), int(itemsize)))
 
 
-def hmc_sample(module, cur, init, mass_kind, inv_mass, mass_factor, L, eps, n_traj, traj_offset, burn, seed, chain_offset,
-               samples, reject_count, workspace, H_old=None, H_new=None, accept=None, resume=False, pre=None):
-    """hta_jit_hmc_sample: trajectories [traj_offset, traj_offset + n_traj) on the compiled callback, one launch."""
+def _fill_common(a, cur, init, inv_mass, mass_factor, L, eps, n_traj, traj_offset, burn, seed, chain_offset, samples, reject_count,
+                 H_old, H_new, accept, resume, pre=None):
+    """The fields HtaCbHmcArgs and HtaCbRolledArgs share (csrc/jit/jit_args.h: HTA_CB_HMC_FIELDS); returns (C, D)."""
     _abi.require_device(cur, "params")
     C, D = cur.shape
-    a = _abi.HtaCbHmcArgs()
     a.cur, a.init = cur.data_ptr(), _abi._p(init, cur).value
     a.inv_mass = None if inv_mass is None else _abi._p(inv_mass, cur).value
     a.mass_factor = None if mass_factor is None else _abi._p(mass_factor, cur).value
@@ -187,6 +187,15 @@ def hmc_sample(module, cur, init, mass_kind, inv_mass, mass_factor, L, eps, n_tr
     a.resume = 1 if resume else 0
     if pre is not None:
         a.pre, a.pre_bytes = pre.data_ptr(), pre.numel() * pre.element_size()
+    return C, D
+
+
+def hmc_sample(module, cur, init, mass_kind, inv_mass, mass_factor, L, eps, n_traj, traj_offset, burn, seed, chain_offset,
+               samples, reject_count, workspace, H_old=None, H_new=None, accept=None, resume=False, pre=None):
+    """hta_jit_hmc_sample: trajectories [traj_offset, traj_offset + n_traj) on the compiled callback, one launch."""
+    a = _abi.HtaCbHmcArgs()
+    C, D = _fill_common(a, cur, init, inv_mass, mass_factor, L, eps, n_traj, traj_offset, burn, seed, chain_offset, samples, reject_count,
+                        H_old, H_new, accept, resume, pre)
     with torch.cuda.device(cur.device):
         _abi._check(_abi.load().hta_jit_hmc_sample(module.handle, ctypes.byref(a), D, cur.element_size(), int(mass_kind),
                                                    workspace.data_ptr(), workspace.numel() * workspace.element_size(),
@@ -272,22 +281,9 @@ def rolled_sample(module, cur, init, U, tables, rows, waves, mass_kind, inv_mass
                   chain_offset, samples, reject_count, workspace, H_old=None, H_new=None, accept=None, resume=False, pre=None):
     """hta_jit_rolled_sample: trajectories [traj_offset, traj_offset + n_traj) on the rolled callback, one launch; `tables` are the
     groups' device tables ([rows, slots] in the run's dtype), `waves` the waves per workgroup of 64 chains."""
-    _abi.require_device(cur, "params")
-    C, D = cur.shape
     a = _abi.HtaCbRolledArgs()
-    a.cur, a.init = cur.data_ptr(), _abi._p(init, cur).value
-    a.inv_mass = None if inv_mass is None else _abi._p(inv_mass, cur).value
-    a.mass_factor = None if mass_factor is None else _abi._p(mass_factor, cur).value
-    a.samples = None if samples is None else _abi._p(samples, cur).value
-    a.reject_count = reject_count.data_ptr()
-    a.H_old = None if H_old is None else _abi._p(H_old, cur).value
-    a.H_new = None if H_new is None else _abi._p(H_new, cur).value
-    a.accept = None if accept is None else accept.data_ptr()
-    a.C, a.eps, a.seed, a.chain_offset = C, float(eps), int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_offset)
-    a.L, a.n_traj, a.traj_offset, a.burn = int(L), int(n_traj), int(traj_offset), int(burn)
-    a.resume = 1 if resume else 0
-    if pre is not None:
-        a.pre, a.pre_bytes = pre.data_ptr(), pre.numel() * pre.element_size()
+    C, D = _fill_common(a, cur, init, inv_mass, mass_factor, L, eps, n_traj, traj_offset, burn, seed, chain_offset, samples, reject_count,
+                        H_old, H_new, accept, resume, pre)
     for k, (t, r) in enumerate(zip(tables, rows)):
         a.table[k], a.rows[k] = _abi._p(t, cur).value, int(r)
     a.waves = int(waves)
@@ -328,20 +324,10 @@ def split_workspace_bytes(C, D, itemsize):
 def split_sample(module, cur, init, M, split_kind, mass_kind, inv_mass, mass_factor, L, eps, n_traj, traj_offset, burn, seed,
                  chain_offset, samples, reject_count, workspace, H_old=None, H_new=None, accept=None, resume=False):
     """hta_jit_split_sample: trajectories [traj_offset, traj_offset + n_traj) of a split integrator on the compiled list, one launch."""
-    _abi.require_device(cur, "params")
-    C, D = cur.shape
     a = _abi.HtaCbHmcArgs()
-    a.cur, a.init = cur.data_ptr(), _abi._p(init, cur).value
-    a.inv_mass = None if inv_mass is None else _abi._p(inv_mass, cur).value
-    a.mass_factor = None if mass_factor is None else _abi._p(mass_factor, cur).value
-    a.samples = None if samples is None else _abi._p(samples, cur).value
-    a.reject_count = reject_count.data_ptr()
-    a.H_old = None if H_old is None else _abi._p(H_old, cur).value
-    a.H_new = None if H_new is None else _abi._p(H_new, cur).value
-    a.accept = None if accept is None else accept.data_ptr()
-    a.C, a.eps, a.seed, a.chain_offset = C, float(eps), int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_offset)
-    a.L, a.n_traj, a.traj_offset, a.burn = int(L), int(n_traj), int(traj_offset), int(burn)
-    a.resume, a.split_kind = (1 if resume else 0), int(split_kind)
+    C, D = _fill_common(a, cur, init, inv_mass, mass_factor, L, eps, n_traj, traj_offset, burn, seed, chain_offset, samples, reject_count,
+                        H_old, H_new, accept, resume)
+    a.split_kind = int(split_kind)
     with torch.cuda.device(cur.device):
         _abi._check(_abi.load().hta_jit_split_sample(module.handle, ctypes.byref(a), D, int(M), cur.element_size(), int(mass_kind),
                                                      int(split_kind), workspace.data_ptr(), workspace.numel() * workspace.element_size(),

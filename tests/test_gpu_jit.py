@@ -374,3 +374,94 @@ def test_predrawn_records_equal_the_in_lane_draw(ht, monkeypatch):
     assert "hta_cb_hmc_kernel" in route() and "predrawn" not in route()
     bad = compare(a, [x.cpu().numpy() for x in b], 1e-9, 0.02)
     assert torch.equal(acc_a.cpu()[~bad], acc_b.cpu()[~bad])
+
+
+# ---- the end of a trajectory at a launch boundary: plain, rolled and split kernels at one shape -------------------------------
+TAIL = dict(C=65, D=3, M=2, ROWS=8, N=8, L=5, burn=3, first=5)
+# (eps, seed) chosen with the oracle: at trajectory burn + 1 = 4 the plain integrator accepts 32 of the 65 chains and rejects 33 -
+# chain 64, the one live lane of the second wave, among the rejected - and the symmetric split accepts 51 and rejects 14
+TAIL_EPS, TAIL_SEED = 0.8, 3
+_tail_ref = {}
+
+
+def _tail_data():
+    rng = np.random.default_rng(0)
+    n = TAIL["M"] * TAIL["ROWS"]
+    return rng.standard_normal((n, TAIL["D"])), (rng.uniform(size=n) > 0.5).astype(np.float64)
+
+
+def _tail_closure(rows):
+    """Logistic regression on `rows` of the 16 with its share of the prior -0.5 |w|^2: a plain closure over device tensors."""
+    X, y = _tail_data()
+    A, yy, w = tt(X[rows], torch.float64), tt(y[rows], torch.float64), len(rows) / len(y)
+
+    def f(th):
+        z = A @ th
+        return (yy * z - torch.nn.functional.softplus(z)).sum() - 0.5 * w * (th * th).sum()
+    return f
+
+
+def _tail_numpy(rows):
+    X, y = _tail_data()
+    A, yy, w = X[rows], y[rows], len(rows) / len(y)
+    return (lambda th: ((th @ A.T) * yy - np.logaddexp(0, th @ A.T)).sum(-1) - 0.5 * w * (th * th).sum(-1),
+            lambda th: (yy - 1 / (1 + np.exp(-(th @ A.T)))) @ A - w * th)
+
+
+def _tail_oracle(split, th0):
+    """The oracle's run of the whole likelihood (plain, rolled) or of its two halves under the symmetric split: computed once."""
+    if split not in _tail_ref:
+        t = TAIL
+        draws = O.PhiloxDraws(TAIL_SEED, np.arange(t["C"]), np.float64)
+        halves = [np.arange(m * t["ROWS"], (m + 1) * t["ROWS"]) for m in range(t["M"])]
+        if split:
+            fs = [_tail_numpy(r) for r in halves]
+            _tail_ref[split] = O.sample_hmc(None, th0, t["N"], t["L"], TAIL_EPS, t["burn"], None, draws, grad_fns=[f[1] for f in fs],
+                                            logp_fns=[f[0] for f in fs], split_kind="symmetric")
+        else:
+            whole = type("Whole", (), {})()
+            whole.logp, whole.grad = _tail_numpy(np.concatenate(halves))
+            _tail_ref[split] = O.sample_hmc(whole, th0, t["N"], t["L"], TAIL_EPS, t["burn"], None, draws)
+        q2 = _tail_ref[split][1]["accept"][t["burn"] + 1]
+        assert q2.any() and not q2.all()                     # both branches of the tail are taken at the launch boundary
+    return _tail_ref[split]
+
+
+@pytest.mark.parametrize("kernel,tol,max_bad", [("plain", 1e-9, 0.03), ("rolled", 1e-8, 0.02), ("split", 1e-9, 0.03)])
+def test_a_launch_that_ends_on_the_q2_trajectory(ht, kernel, tol, max_bad, monkeypatch):
+    """65 chains (a second wave with ONE live lane, its idle lanes shadow the last chain), float64, burn = 3, 8 trajectories, cut into
+    two launches so that the first ends with trajectory burn + 1: the Q2 reset falls on the last pass of a launch, the refreshed
+    carried values reach the second launch through the workspace (the extra pass t == n_traj), and chains that accepted there resume
+    from theirs.  The two-launch run equals the one-launch run bit for bit, reject counts included, and both equal the oracle at the
+    tolerance of the kernel's own parity test."""
+    from hamiltorch_amd import samplers
+    t = TAIL
+    all_rows = np.arange(t["M"] * t["ROWS"])
+    if kernel == "split":
+        fn = [_tail_closure(all_rows[m * t["ROWS"]:(m + 1) * t["ROWS"]]) for m in range(t["M"])]
+        cls, kw, name = samplers._CompiledSplitHMC, dict(integrator=ht.Integrator.SPLITTING), "hta_cb_split_kernel<D=3,M=2,f64,mass=0,kind=symmetric"
+    else:
+        fn = _tail_closure(all_rows)
+        cls, kw, name = samplers._CompiledHMC, {}, "hta_cb_hmc_kernel<D=3,f64"
+        if kernel == "rolled":
+            monkeypatch.setenv("HAMILTORCH_AMD_JIT_ROLL", "force")
+            monkeypatch.setattr(samplers._CompiledRolledHMC, "WAVES", 2)
+            name = "hta_cb_rolled_kernel<D=3,rows=16,W=2,f64"
+    th0 = start(t["C"], t["D"], TAIL_SEED, torch.float64)
+    kw.update(num_samples=t["N"], num_steps_per_sample=t["L"], step_size=TAIL_EPS, burn=t["burn"], seed=TAIL_SEED, debug=2, verbose=False)
+    one, acc_one = ht.sample(fn, tt(th0, torch.float64), **kw)
+    assert name in route(), route()
+    whole, launches = cls.advance, []
+
+    def in_two(self, n0, count, *a, **k):
+        launches.append((n0, count))
+        whole(self, n0, t["first"], *a, **k)
+        whole(self, n0 + t["first"], count - t["first"], *a, **k)
+    monkeypatch.setattr(cls, "advance", in_two)
+    two, acc_two = ht.sample(fn, tt(th0, torch.float64), **kw)
+    assert name in route() and launches == [(0, t["N"])], (route(), launches)
+    assert torch.equal(torch.stack(list(one)), torch.stack(list(two))) and torch.equal(acc_one, acc_two)
+    ref, info = _tail_oracle(kernel == "split", th0)
+    assert len(one) == len(ref) == t["N"] - t["burn"]
+    bad = compare(one, ref, tol, max_bad)
+    np.testing.assert_allclose(acc_one.cpu().numpy()[~bad], info["acc_rate"][~bad], atol=1e-12)

@@ -286,3 +286,17 @@ def test_emitted_literals_round_trip():
     assert emit.literal(1.0, "double") == "1.0" and emit.literal(1e300, "float").endswith("huge_val()")
     assert "nan" in emit.literal(float("nan"), "double") and emit.literal(-math.inf, "float").startswith("(-")
     assert float(emit.literal(1 / 3, "double")) == 1 / 3
+
+
+def test_argument_blocks_keep_their_layout():
+    """The ctypes side of the static_asserts in csrc/jit/jit_args.h: HtaCbHmcArgs is 160 bytes, HtaCbRolledArgs starts with the same
+    fields at the same offsets, and its tables, row counts and wave count follow at 160, 192 and 208."""
+    import ctypes
+    from hamiltorch_amd import _abi
+    H, R = _abi.HtaCbHmcArgs, _abi.HtaCbRolledArgs
+    assert ctypes.sizeof(H) == 160 and ctypes.sizeof(R) == 216
+    assert len(H._fields_) == 23 and [n for n, _ in R._fields_[:23]] == [n for n, _ in H._fields_]
+    for name, _ in H._fields_:
+        assert getattr(R, name).offset == getattr(H, name).offset and getattr(R, name).size == getattr(H, name).size, name
+    assert (H.pre.offset, H.pre_bytes.offset) == (144, 152)
+    assert (R.table.offset, R.rows.offset, R.waves.offset) == (160, 192, 208)
