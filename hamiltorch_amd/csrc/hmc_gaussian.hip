@@ -737,10 +737,19 @@ __global__ __launch_bounds__(256) void hmc_gauss_eig_kernel(GaussArgs<T> a, cons
 // Developer builds only (profiles/r05y_quad_ablation.txt: timing of the trajectory's parts, wrong samples): -DQUAD_FUSED_NS=n -DQUAD_SLOTS=m (a deeper
 // record look-ahead: measured, no effect), -DQUAD_ABLATE_STORE / _LOAD / _ACC / _TAIL (one cost of a trajectory removed at a time),
 // -DQUAD_ABLATE_ROWS (profiles/r07a_quad_rows.txt: the integrating wave of "quad_rows" with nobody reading its ring), -DQUAD_ABLATE_LOCAL
-// (profiles/r08a_quad_local.txt: the local launch whose producer waves draw nothing), -DQUAD_ROWS_NI=1|4
+// (profiles/r08a_quad_local.txt: the local launch whose producer waves draw nothing), -DQUAD_ABLATE_WIDE (below), -DQUAD_ROWS_NI=1|4
 // (the other placements of the row waves: correct samples).
 #ifndef QUAD_SLOTS
 #define QUAD_SLOTS 4
+#endif
+// -DQUAD_ABLATE_WIDE (profiles/r11a_quad_wide.txt, timing only, wrong samples): the gate of "quad_wide" - in hmc_gauss_quad_local_kernel
+// the integrating wave issues its record read and its message write only at position P % 4 == 3 of a group, as one 16-byte access
+// each (junk data, lane base x 16 bytes), the other positions pad the wait state with s_nop; barriers untouched, the row wave
+// ignores the status message.
+#if defined(QUAD_ABLATE_WIDE)
+constexpr bool QUAD_ABLATE_WIDE_ON = true;
+#else
+constexpr bool QUAD_ABLATE_WIDE_ON = false;
 #endif
 constexpr int QUAD_SLOTS_MAX = QUAD_SLOTS;     // record look-ahead of the quad kernel = rows of slack in the workspace
 template <int CTRL> __device__ __forceinline__ float dpp_f(float v) {
@@ -830,13 +839,24 @@ template <int NS, int NU, typename F> __device__ __forceinline__ void quad_local
     while (t < t_end) { f(t, phase, one, plain); t += 1; }
   }
 }
-template <int D, bool DIAG, int LB, int VAR, bool FUSED, bool ROWS = false, bool LOCAL = false>
+// WIDE (hmc_gauss_quad_wide_kernel below, tuning key "quad_wide") is LOCAL with 16-byte hand-overs: both rings keep their sizes, but
+// position p WITHIN ITS GROUP lives at (p >> 2) * 1024 + lane * 16 + (p & 3) * 4 of a buffer (lane: the integrating wave's), so the
+// four positions of a block of four are one ds_read_b128 / ds_write_b128 per lane.  The integrating wave reads the records of block
+// b + 1 inside the first trajectory of block b into the other half of eight record registers (one wait per block) and writes the
+// four messages of a block with the select that completes it (or in the hand-over); the butterfly's wait states that were LDS
+// instructions are one "s_nop 1".  The 16-byte accesses are typed LDS accesses the compiler sees: it keeps their wait counts and
+// the hazard of a wide store's data registers.  Arithmetic, the sequence of groups (quad_local_groups) and the number and order of
+// s_barriers of every role are exactly LOCAL's - only addresses and LDS instructions differ, so there is no new way to hang.
+template <int D, bool DIAG, int LB, int VAR, bool FUSED, bool ROWS = false, bool LOCAL = false, bool WIDE = false>
 __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t gt, const QuadFused fz,
                                           uint32_t lds = 0, uint32_t recl = 0) {
   typedef float T;
   constexpr bool UADDR = (VAR & 1) != 0, NOGUARD = (VAR & 2) != 0, TAIL = (VAR & 4) != 0;
   static_assert(!ROWS || (FUSED && UADDR && TAIL && !DIAG), "the row-wave form is an instance of the fused launch");
   static_assert(!LOCAL || (ROWS && D < 4), "the local launch is the row-wave form with one record vector");
+  static_assert(!WIDE || (LOCAL && QUAD_FUSED_NS == 4), "the wide hand-over is the local launch's, in blocks of four positions");
+  typedef float V4f __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(3))) V4f* lvec_t;
   const bool on = (gt >> 2) < a.C;
   const int64_t c = ROWS ? (on ? gt >> 2 : a.C - 1) : gt >> 2;       // ROWS: every wave stays for the barriers
   const int k = (int)(gt & 3);
@@ -927,11 +947,17 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   // an HBM load takes to return, and the look-ahead has to cover it.  The workspace carries QUAD_SLOTS_MAX rows of slack.
   constexpr int NS = quad_fused_ns(LB, FUSED);     // (FUSED: the records come from memory, not from this XCD's L2)
   static_assert(NS <= QUAD_SLOTS_MAX, "workspace slack");
-  T zs[NS], lus[NS];
+  constexpr int NZ = WIDE ? 8 : NS;                // (WIDE: the block being consumed and the block being read)
+  T zs[NZ], lus[NZ];
+  T mq[4] = {0.f, 0.f, 0.f, 0.f};                  // WIDE: the messages of the block being completed
+#if defined(QUAD_ABLATE_WIDE)
+  const V4f wzero = {0.f, 0.f, 0.f, 0.f};
+  V4f wjunk = wzero;
+#endif
   need_rows(NS - 1);
   if constexpr (LOCAL) {
 #pragma unroll
-    for (int i = 0; i < NS; ++i) zs[i] = lus[i] = 0.f;      // (begin() below reads the first records of every group)
+    for (int i = 0; i < NZ; ++i) zs[i] = lus[i] = 0.f;      // (begin() below reads the first records of every group)
   } else {
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
@@ -955,10 +981,13 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   uint64_t pend_mask = 0;
   auto handover = [&](auto G) {                  // after a group of G trajectories
     if constexpr (ROWS) {
-      if constexpr (D < 4) {
+      if constexpr (WIDE && decltype(G)::value >= 4) {      // the group's last message completes its last block
+        asm volatile("v_cndmask_b32_e64 %0, -1, %1, %2" : "=v"(mq[3]) : "v"(pend_y), "s"(pend_mask));
+        *(lvec_t)(uintptr_t)(lds + (uint32_t)((decltype(G)::value / 4 - 1) * 1024)) = V4f{mq[0], mq[1], mq[2], mq[3]};
+      } else if constexpr (D < 4) {                          // (WIDE: a group of one is slot 0 of block 0 - the same dword)
         T msg;
         asm volatile("v_cndmask_b32_e64 %0, -1, %1, %2\n\tds_write_b32 %3, %0 offset:%4"
-                     : "=&v"(msg) : "v"(pend_y), "s"(pend_mask), "v"(lds), "n"((decltype(G)::value - 1) * 256));
+                     : "=&v"(msg) : "v"(pend_y), "s"(pend_mask), "v"(lds), "n"(QUAD_ABLATE_WIDE_ON && LOCAL ? ((decltype(G)::value - 1) >> 2) * 1024 : (decltype(G)::value - 1) * 256));
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       lds = lds_both - lds;
@@ -971,7 +1000,10 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   // trajectory P + NS - never past the group: the other buffer is being written.
   typedef const __attribute__((address_space(3))) T* lrec_t;
   auto begin = [&](auto G) {
-    if constexpr (LOCAL) {
+    if constexpr (WIDE && decltype(G)::value >= 4) {      // block 0 of the group; block b + 1 is read inside the first trajectory of block b
+      const V4f v = *(lvec_t)(uintptr_t)recl;
+      zs[0] = v[0]; zs[1] = v[1]; zs[2] = v[2]; zs[3] = v[3];
+    } else if constexpr (LOCAL) {                           // (WIDE: a group of one is slot 0 of block 0 - the same dword)
 #pragma unroll
       for (int i = 0; i < (decltype(G)::value < NS ? decltype(G)::value : NS); ++i)      // (volatile: four ds_read_b32, not two paired reads - the loop's count is pinned)
         zs[i] = *(const volatile __attribute__((address_space(3))) T*)(uintptr_t)(recl + (uint32_t)i * 256u);
@@ -1075,6 +1107,74 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
           // carry and pads with two.
           qp = 0.f;
           constexpr int P = decltype(pos)::value;
+          if constexpr (WIDE) {
+            // The same blocks with the LDS instructions once per block of four positions: the select of trajectory P - 1's message
+            // targets mq[(P - 1) % 4]; the select of a block's last message (P % 4 == 0, P > 0) is followed by the 16-byte write of
+            // the block, and the first trajectory of a block reads the records of the next block of the group into the other half
+            // of zs.  A trajectory that issues no LDS instruction (three of four) has its tail in ONE asm block, the second stage's
+            // two wait states being one "s_nop 1" (the compiler pads between two blocks).  The first trajectory of a block keeps
+            // the local launch's form: the typed LDS accesses (or an "s_nop 0") sit between two volatile asm blocks and are the
+            // wait states of the second stage; tests/test_quad_wide_resources.py checks in the built code that every second
+            // stage has its two wait states.
+            constexpr int Gs = decltype(grp)::value;
+            constexpr bool rd = P % 4 == 0 && P + 4 < Gs, wr = P % 4 == 0 && P > 0;
+#define HTA_WB1 "\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+#define HTA_WT2 "\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_cmp_ge_f32_e64 %3, %0, %1" \
+                "\n\tv_cndmask_b32_e64 %2, %2, %5, %3"
+            if constexpr (!rd && !wr && P > 0) {
+              asm volatile("v_cndmask_b32_e64 %4, -1, %7, %3\n\tv_mov_b32_dpp %1, %6 quad_perm:[%8,%8,%8,%8] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                           HTA_WB1 "\n\ts_nop 1" HTA_WT2
+                           : "+v"(dH), "=&v"(logu), "+v"(yc), "+s"(pend_mask), "=&v"(mq[(P + 3) % 4])
+                           : "v"(y), "v"(slot), "v"(pend_y), "n"(D));
+            } else if constexpr (!rd && !wr) {
+              T none;
+              asm volatile("v_mov_b32_dpp %1, %6 quad_perm:[%8,%8,%8,%8] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\ts_nop 0"
+                           HTA_WB1 "\n\ts_nop 1" HTA_WT2
+                           : "+v"(dH), "=&v"(logu), "+v"(yc), "+s"(pend_mask), "=&v"(none)
+                           : "v"(y), "v"(slot), "v"(pend_y), "n"(D));
+            } else {
+              if constexpr (wr) {
+                asm volatile("v_cndmask_b32_e64 %2, -1, %4, %5\n\tv_mov_b32_dpp %1, %3 quad_perm:[%6,%6,%6,%6] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                             HTA_WB1
+                             : "+v"(dH), "=&v"(logu), "=&v"(mq[3]) : "v"(slot), "v"(pend_y), "s"(pend_mask), "n"(D));
+                *(lvec_t)(uintptr_t)(lds + (uint32_t)((P / 4 - 1) * 1024)) = V4f{mq[0], mq[1], mq[2], mq[3]};
+              } else {
+                asm volatile("v_mov_b32_dpp %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\ts_nop 0" HTA_WB1 "\n\ts_nop 0"
+                             : "+v"(dH), "=&v"(logu) : "v"(slot), "n"(D));
+              }
+              if constexpr (rd) {
+                constexpr int nb = P / 4 + 1;
+                const V4f v = *(lvec_t)(uintptr_t)(recl + (uint32_t)(nb * 1024));
+                zs[(nb % 2) * 4] = v[0]; zs[(nb % 2) * 4 + 1] = v[1]; zs[(nb % 2) * 4 + 2] = v[2]; zs[(nb % 2) * 4 + 3] = v[3];
+              } else asm volatile("s_nop 0");
+              asm volatile("v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_cmp_ge_f32_e64 %2, %0, %3\n\t"
+                           "v_cndmask_b32_e64 %1, %1, %4, %2"
+                           : "+v"(dH), "+v"(yc), "=&s"(pend_mask) : "v"(logu), "v"(y));
+            }
+            // (the select of potc is a block of its own, free to sink to potc's next use; the compiler pads one wait state between
+            //  the block above and the next trajectory's first FMA, which reads yc - where the local launch has its s_waitcnt)
+            asm volatile("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(potc) : "v"(pot1), "s"(pend_mask));
+#undef HTA_WB1
+#undef HTA_WT2
+            pend_y = y;
+          } else {
+#if defined(QUAD_ABLATE_WIDE)      // timing only (profiles/r11a_quad_wide.txt): the message write once per four positions as ONE 16-byte write of junk, the others pad
+          if constexpr (LOCAL && P > 0) {
+            T msg;
+            if constexpr (P % 4 == 3)
+              asm volatile("v_cndmask_b32_e64 %2, -1, %4, %5\n\tv_mov_b32_dpp %1, %3 quad_perm:[%8,%8,%8,%8] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                           "\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                           "\n\tds_write_b128 %6, %9 offset:%7"
+                           : "+v"(dH), "=&v"(logu), "=&v"(msg)
+                           : "v"(slot), "v"(pend_y), "s"(pend_mask), "v"(lds), "n"((P >> 2) * 1024), "n"(D), "v"(wzero));
+            else
+              asm volatile("v_cndmask_b32_e64 %2, -1, %4, %5\n\tv_mov_b32_dpp %1, %3 quad_perm:[%6,%6,%6,%6] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                           "\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                           "\n\ts_nop 0"
+                           : "+v"(dH), "=&v"(logu), "=&v"(msg)
+                           : "v"(slot), "v"(pend_y), "s"(pend_mask), "n"(D));
+          } else
+#endif
           if constexpr (P > 0) {
             T msg;
             asm volatile("v_cndmask_b32_e64 %2, -1, %4, %5\n\tv_mov_b32_dpp %1, %3 quad_perm:[%8,%8,%8,%8] row_mask:0xf bank_mask:0xf bound_ctrl:1"
@@ -1089,8 +1189,16 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
           if constexpr (LOCAL) {
             // the refill is an LDS read the compiler sees and waits for (the message writes it does not see only make its count
             // stricter: LDS returns in order); the last NS trajectories of a group have nothing to read and pad the wait state
+#if defined(QUAD_ABLATE_WIDE)      // timing only: ONE 16-byte read per four positions, waited for four trajectories later (nobody uses it: the slots keep begin()'s records)
+            if constexpr (P % 4 == 3 && P + NS < decltype(grp)::value) {
+              asm volatile("" :: "v"(wjunk));
+              wjunk = *(lvec_t)(uintptr_t)(recl + (uint32_t)(((P + 1) >> 2) * 1024));
+            }
+            else asm volatile("s_nop 0");
+#else
             if constexpr (P + NS < decltype(grp)::value) slot = *(lrec_t)(uintptr_t)(recl + (uint32_t)(P + NS) * 256u);
             else asm volatile("s_nop 0");
+#endif
           } else {
           asm volatile("" : "+v"(roff[pos]));            // keeps the zero-extension next to its use: base + 32-bit offset addressing
           slot = *(grec_t)(recb + roff[pos]);
@@ -1100,6 +1208,7 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
                        "v_cndmask_b32_e64 %1, %1, %5, %3\n\tv_cndmask_b32_e64 %2, %2, %6, %3"
                        : "+v"(dH), "+v"(yc), "+v"(potc), "=&s"(pend_mask) : "v"(logu), "v"(y), "v"(pot1));
           pend_y = y;                                    // its message: inside the next trajectory's block, or by the hand-over
+          }
         }
         else if constexpr (ROWS) { qp = 0.f; dH = quad_sum(dH); }      // (D = 4: log u is a second record element; the compiler pads the DPP wait states)
         else if constexpr (D == 1)
@@ -1211,7 +1320,7 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
         asm volatile("s_barrier" ::: "memory");
         quad_local_groups<NS, NU>(a, [&](int, int, auto G, auto q2) {
           begin(G);
-          quad_static_for<0, decltype(G)::value>([&](auto I) { trajectory(zs[I % NS], lus[I % NS], q2, I, G); });
+          quad_static_for<0, decltype(G)::value>([&](auto I) { trajectory(zs[I % NZ], lus[I % NZ], q2, I, G); });
           handover(G);
         });
       }
@@ -1275,7 +1384,7 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
 // The row wave of an integrating wave (ROWS above): same lane, same chain, same coordinate.  It walks the groups of trajectories in
 // the integrator's order, one barrier in front of each, and owns the output side.  In the burn-in phase it stores no row (the
 // one-launch form rewrites the chain's slot of `theta` every trajectory; nobody reads those within the launch): only the final state.
-template <int D, int LB, bool LOCAL = false>
+template <int D, int LB, bool LOCAL = false, bool WIDE = false>
 __device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t gt, uint32_t lds) {
   typedef float T;
   constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
@@ -1314,7 +1423,14 @@ __device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const 
   auto group = [&](auto G, bool q2) {
     asm volatile("s_barrier" ::: "memory");      // the integrator has filled this buffer
     constexpr int g = decltype(G)::value;
-    if constexpr (g % 4 == 0) {
+    if constexpr (WIDE && g % 4 == 0) {           // one 16-byte read per block of four positions (quad_body: WIDE)
+      for (int i = 0; i < g; i += 4) {
+        typedef float V4f __attribute__((ext_vector_type(4)));
+        V4f m;
+        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(m) : "v"(lds + (uint32_t)i * 256u) : "memory");
+        take(m[0], false); take(m[1], false); take(m[2], false); take(m[3], false);
+      }
+    } else if constexpr (g % 4 == 0) {
       for (int i = 0; i < g; i += 4) {
         T m0, m1, m2, m3;
         asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:256\n\tds_read_b32 %2, %4 offset:512\n\tds_read_b32 %3, %4 offset:768\n\t"
@@ -1352,6 +1468,7 @@ __device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const 
   }
   uint32_t starved;
   asm volatile("s_barrier\n\tds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(starved) : "v"(lds) : "memory");
+  if (QUAD_ABLATE_WIDE_ON && LOCAL) starved = 0u;      // (the ceiling build's rings hold junk)
   if (__builtin_expect(starved != 0u, 0)) {     // see QuadFused: the rows of this launch and the chain state become NaN
     qc = __builtin_nanf("");
     if (a.samples && on) {
@@ -1490,25 +1607,33 @@ __global__ __launch_bounds__(quad_fused_threads(NI)) void hmc_gauss_quad_fused_k
 //              barrier in front of the first group.  All roles walk quad_local_groups.
 // Results are bit-identical to the cross-block launch (tests/test_gpu_quad_local.py).  -DQUAD_ABLATE_LOCAL (developer builds, timing
 // only, wrong samples: profiles/r08a_quad_local.txt): the producer waves draw nothing - the ceiling of the integrator's side.
-template <int D, int LB>
+// WIDE (quad_body: WIDE): element k of the record of position p goes to the integrating lane chain * 4 + k of block p >> 2, slot p & 3 -
+// four dwords 16 bytes apart; a sweep of eight positions is two blocks.
+template <int D, int LB, bool WIDE = false>
 __device__ __forceinline__ void quad_local_produce(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t c0, const uint32_t recl,
                                                    const int pl) {
   constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
   static_assert(rec_elems<float, D>() == 4, "one 16-byte record");
   typedef float V4f __attribute__((ext_vector_type(4)));
   typedef __attribute__((address_space(3))) V4f* lvec_t;
+  typedef __attribute__((address_space(3))) float* lflt_t;
   (void)(lvec_t)nullptr;
   const int chain = pl & 15, p0 = pl >> 4;                                      // 128 lanes: eight positions of 16 chains per sweep
   const int64_t c = min(c0 + chain, a.C - 1);                                   // (past a.C: the last chain again, as the integrator does)
   const uint64_t gchain = a.chain_offset + (uint64_t)c;
-  uint32_t dst = recl + (uint32_t)(p0 * 256 + chain * 16);
+  uint32_t dst = recl + (WIDE ? (uint32_t)((p0 >> 2) * 1024 + chain * 64 + (p0 & 3) * 4) : (uint32_t)(p0 * 256 + chain * 16));
   const uint32_t dst_both = 2u * dst + (uint32_t)(NU * 256);
   quad_local_groups<NS, NU>(a, [&](int t0, int, auto G, auto) {
 #if !defined(QUAD_ABLATE_LOCAL)
     for (int p = p0; p < decltype(G)::value; p += 8) {
       float rec[4];
       quad_make_record<D>(a.seed, gchain, (uint32_t)(a.traj_offset + t0 + p), eig, rec);
-      *(lvec_t)(uintptr_t)(dst + (uint32_t)((p - p0) * 256)) = V4f{rec[0], rec[1], rec[2], rec[3]};
+      if constexpr (WIDE) {
+        const lflt_t w = (lflt_t)(uintptr_t)(dst + (uint32_t)((p - p0) * 256));      // (eight positions on: two blocks of 1024 bytes)
+        w[0] = rec[0]; w[4] = rec[1]; w[8] = rec[2]; w[12] = rec[3];
+      } else {
+        *(lvec_t)(uintptr_t)(dst + (uint32_t)((p - p0) * 256)) = V4f{rec[0], rec[1], rec[2], rec[3]};
+      }
     }
 #endif
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // publishes this group's records
@@ -1525,10 +1650,28 @@ __global__ __launch_bounds__(256) void hmc_gauss_quad_local_kernel(GaussArgs<flo
   const int64_t gt = (int64_t)blockIdx.x * 64 + lane;
   if (wave == 0) {
     __builtin_amdgcn_s_setprio(3);
-    quad_body<D, false, LB, 7, true, true, true>(a, eig, gt, QuadFused{nullptr, 1, 0u, 0, nullptr, 0}, msgs + (uint32_t)lane * 4u, recs + (uint32_t)lane * 4u);
+    quad_body<D, false, LB, 7, true, true, true>(a, eig, gt, QuadFused{nullptr, 1, 0u, 0, nullptr, 0}, msgs + (uint32_t)lane * (QUAD_ABLATE_WIDE_ON ? 16u : 4u), recs + (uint32_t)lane * (QUAD_ABLATE_WIDE_ON ? 16u : 4u));
   }
   else if (wave == 1) quad_rows_body<D, LB, true>(a, eig, gt, msgs + (uint32_t)lane * 4u);
   else quad_local_produce<D, LB>(a, eig, (int64_t)blockIdx.x * 16, recs, (int)threadIdx.x - 128);
+}
+// WIDE (tuning key "quad_wide"): the local launch - the same roles, rings of the same sizes, the same groups and barriers - with
+// 16-byte hand-overs per block of four positions (quad_body: WIDE); a lane's base in a block of either ring is lane x 16 bytes.
+// Results are bit-identical to the local launch (tests/test_gpu_quad_wide.py).
+template <int D, int LB>
+__global__ __launch_bounds__(256) void hmc_gauss_quad_wide_kernel(GaussArgs<float> a, const float* __restrict__ eig) {
+  constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
+  static_assert(NS == 4 && NU % 4 == 0, "groups are whole blocks of four positions, or single ones");
+  __shared__ __attribute__((aligned(16))) float ring[2 * NU * 64 + 2 * NU * 64];      // as the local launch's: messages | records, two passes each
+  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+  const uint32_t msgs = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)ring, recs = msgs + (uint32_t)(2 * NU * 256);
+  const int64_t gt = (int64_t)blockIdx.x * 64 + lane;
+  if (wave == 0) {
+    __builtin_amdgcn_s_setprio(3);
+    quad_body<D, false, LB, 7, true, true, true, true>(a, eig, gt, QuadFused{nullptr, 1, 0u, 0, nullptr, 0}, msgs + (uint32_t)lane * 16u, recs + (uint32_t)lane * 16u);
+  }
+  else if (wave == 1) quad_rows_body<D, LB, true, true>(a, eig, gt, msgs + (uint32_t)lane * 16u);
+  else quad_local_produce<D, LB, true>(a, eig, (int64_t)blockIdx.x * 16, recs, (int)threadIdx.x - 128);
 }
 
 template <typename T, int D, int MASS>
@@ -1900,6 +2043,8 @@ constexpr int QUAD_STATUS_OFF = QUAD_FUSED_OFF + QUAD_FUSED_CHUNKS + 1;         
 static_assert(QUAD_STATUS_OFF < 128, "the status word lives in the eig block's free tail");
 int g_quad_rows = 1;         // tuning key "quad_rows" (default 1): the fused launch hands the sample rows to row waves through LDS (quad_body: ROWS); 0 = every consumer wave stores its own
 int g_quad_local = 1;        // tuning key "quad_local" (default 1): with "quad_rows" and D <= 3 the records are drawn by producer waves of the consumer's own block (hmc_gauss_quad_local_kernel); 0 = producer blocks behind the consumers', the parity partner
+int g_quad_wide = 1;         // tuning key "quad_wide" (default 1): the local launch hands records and messages over in 16-byte LDS accesses per block of four trajectories (hmc_gauss_quad_wide_kernel); 0 = the 4-byte hand-overs of hmc_gauss_quad_local_kernel, the parity partner
+int g_quad_wide_launches = 0; // debug key "quad_wide_launches": launches of hmc_gauss_quad_wide_kernel since the keys were last reset (the route string does not tell the two local launches apart; tests/test_gpu_quad_wide.py reads it)
 int g_quad_fused = 1;        // tuning key "quad_fused" (default 1): records produced inside the trajectory launch (prepared workspaces only); 0 = a pre-draw launch in front of it
 template <typename T> static bool eig_block_prepared(const GaussArgs<T>& a, int mass_kind);
 template <typename T> static bool quad_route(const GaussArgs<T>& a);
@@ -1957,7 +2102,14 @@ template <typename T, int D, int MASS> void launch_small(const GaussArgs<T>& a, 
           if (D <= 3 && g_quad_rows && g_quad_local && !g_quad_starve) {
             if constexpr (D <= 3) {
               const int lgrid = (int)((a.C + 15) / 16);                                       // 16 chains per block; the record area of the workspace stays unused
-              if (lbv == 25) hmc_gauss_quad_local_kernel<D, 25><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+              if (g_quad_wide) {                                                              // 16-byte hand-overs (quad_body: WIDE)
+                ++g_quad_wide_launches;
+                if (lbv == 25) hmc_gauss_quad_wide_kernel<D, 25><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+                else if (lbv == 10) hmc_gauss_quad_wide_kernel<D, 10><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+                else if (lbv == 5) hmc_gauss_quad_wide_kernel<D, 5><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+                else hmc_gauss_quad_wide_kernel<D, 0><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+              }
+              else if (lbv == 25) hmc_gauss_quad_local_kernel<D, 25><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
               else if (lbv == 10) hmc_gauss_quad_local_kernel<D, 10><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
               else if (lbv == 5) hmc_gauss_quad_local_kernel<D, 5><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
               else hmc_gauss_quad_local_kernel<D, 0><<<lgrid, 256, 0, s>>>(a, a.ws_logu);

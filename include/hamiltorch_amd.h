@@ -574,7 +574,12 @@ int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int it
  * handed over through LDS - 16 chains per block: one integrating wave, its row wave, two producer waves - so no record travels
  * through memory and the launch does not wait for other blocks; the record area of the workspace stays unused, the status word stays
  * 0: bit-identical results, BASELINE config 2 0.139 -> 0.132 ms per call; 0 = producer blocks behind the consumers' blocks, the parity
- * partner; the debug key "quad_starve" = 1 selects that cross-block launch as well). */
+ * partner; the debug key "quad_starve" = 1 selects that cross-block launch as well),
+ * "quad_wide" (1 default = wherever the "quad_local" launch is taken, its two LDS rings are handed over 16 bytes at a time: a block
+ * of four trajectories is one 16-byte record read and one 16-byte message write on the integrating wave and one 16-byte read on the
+ * row wave - same ring sizes, same groups and barriers, bit-identical results; 0 = the 4-byte hand-overs, the parity partner;
+ * the debug key "quad_wide_launches" counts the launches of that kernel since the keys were last reset: the route string is the
+ * same for both). */
 int hta_set_tuning(const char* key, int value);
 /* current value of a route key; every key back to its default (test fixtures call this between tests: the keys are
  * process-global).  The environment variable HTA_TUNING_DEFAULTS="key=value,..." moves the DEFAULT of the named keys for the
