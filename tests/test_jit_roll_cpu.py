@@ -7,7 +7,9 @@ rolled trajectory kernel (csrc/jit/rolled_callback.hip.in) - no GPU needed.
 * HAMILTORCH_AMD_JIT_ROLL=auto leaves every callable that compiled before on its straight-line text and rolls what was refused
   for its size; the refusals name their numbers; lists, leapfrog paths and the derivative kernels refuse a rolled-only callable;
 * hipRTC builds the kernel for gfx950 in float32 and float64, the info block is as specified, float32 uses no scratch;
-* hta_jit_rolled_sample turns bad arguments down before it looks at a device.
+* hta_jit_rolled_sample turns bad arguments down before it looks at a device;
+* the oracle targets of tests/jit_roll_cases.py (closed-form numpy, what the GPU tests hand to oracle.sample_hmc) against
+  torch.autograd of their callables, and the float32 oracle against the float64 oracle on every float32 run of the GPU tests.
 """
 import ctypes
 import re
@@ -312,3 +314,66 @@ def test_the_entry_point_refuses_bad_arguments_without_a_device():
         assert call(**bad) == -1, bad
         assert why in _abi.last_error() and "module is NULL" not in _abi.last_error(), (bad, _abi.last_error())
     assert lib.hta_jit_rolled_sample(None, None, 3, 0, 1, 8, 0, ptr, 1 << 20, None) == -1
+
+
+# ---- the oracle side of tests/test_gpu_jit_roll.py -------------------------------------------------------------------------------
+@pytest.mark.parametrize("case,D,kw", [("logistic", 3, {}), ("logistic", 3, dict(N=3)), ("hierarchical", 4, {}), ("hierarchical", 4, dict(N=300)),
+                                       ("two_structures", 3, {}), ("two_structures", 3, dict(n=7, n_gauss=19)), ("big_logistic", 4, {})])
+def test_the_oracle_targets_against_autograd(case, D, kw):
+    """The closed forms of jit_roll_cases.py, batched, against torch.autograd of the callable in float64 at a dozen points: the bound of
+    `against_autograd`, 1e-10 relative to 1 + |ref|.  A float32 theta is evaluated in float32 and comes back as float32."""
+    fn = getattr(cases, case)(**kw)
+    tgt = cases.oracle_target(fn)
+    pts = 0.5 * np.random.default_rng(7).standard_normal((12, D))
+    mine = np.concatenate([tgt.logp(pts)[:, None], tgt.grad(pts)], 1)
+    assert mine.shape == (12, 1 + D) and mine.dtype == np.float64
+    for k in range(12):
+        x = torch.tensor(pts[k], dtype=f64, requires_grad=True)
+        v = fn(x)
+        g, = torch.autograd.grad(v, x)
+        ref = np.concatenate([[float(v.detach())], g.numpy()])
+        assert np.all(np.abs(mine[k] - ref) <= 1e-10 * (1.0 + np.abs(ref))), (k, mine[k], ref)
+        one = np.concatenate([[tgt.logp(pts[k])], tgt.grad(pts[k])])                    # a single point, [D]
+        assert np.all(np.abs(one - ref) <= 1e-10 * (1.0 + np.abs(ref)))
+    low = pts.astype(np.float32)
+    assert tgt.logp(low).dtype == np.float32 and tgt.grad(low).dtype == np.float32
+    assert np.all(np.abs(tgt.grad(low) - mine[:, 1:]) <= 1e-4 * (1.0 + np.abs(mine[:, 1:])))
+
+
+def flipped_and_deviation(run):
+    """The float32 oracle against the float64 oracle on the same start, mass matrix and draws: which chains took another accept
+    decision somewhere, and the largest difference per chain."""
+    (a, ia), (b, ib) = run.oracle(torch.float32), run.oracle(torch.float32, exact=True)
+    flipped = (np.stack(ia["accept"]) != np.stack(ib["accept"])).any(0)
+    return flipped, cases.deviation(a, b), ia
+
+
+@pytest.mark.parametrize("name", [n for n in cases.F32_RUNS if n != "long"])
+def test_the_float32_oracle_is_inside_the_band_and_the_cap(name):
+    """Every float32 run of tests/test_gpu_jit_roll.py is judged at 2e-4 with 3 % of the chains exempt.  That judges the kernel only if
+    float32 ARITHMETIC on that run - the oracle evaluated in float32 against the oracle in float64, same draws - is well inside both:
+    no chain that kept its accept decisions beyond a third of the band, flipped chains within a third of the cap (1 chain in 100)."""
+    run = cases.RUNS[name]
+    flipped, err, info = flipped_and_deviation(run)
+    print("%s: %d of %d chains flipped, largest deviation of the others %.3g, acceptance %.2f"
+          % (name, flipped.sum(), flipped.size, err[~flipped].max(), info["acc_rate"].mean()))
+    assert flipped.mean() <= cases.MAX_FLIPPED / 3
+    assert err[~flipped].max() <= cases.TOL[torch.float32] / 3
+    assert (err > cases.TOL[torch.float32]).mean() <= cases.MAX_FLIPPED / 3
+
+
+def test_the_float32_bound_of_the_long_sums():
+    """1500 rows in float32: the bound of test_long_sums is 4 x the deviation of the float32 oracle from the float64 oracle MEASURED
+    here (LONG_F32_MEASURED, recorded next to that test) - this test keeps the record honest: what it measures is not above it, and
+    the run moves (the oracle accepts between 0.5 and 1.0 of its proposals)."""
+    import test_gpu_jit_roll as G
+    run = cases.RUNS["long"]
+    flipped, err, info = flipped_and_deviation(run)
+    print("long: %d of %d chains flipped, largest deviation of the others %.4g, acceptance %.3f"
+          % (flipped.sum(), flipped.size, err[~flipped].max(), info["acc_rate"].mean()))
+    assert flipped.mean() <= cases.MAX_FLIPPED / 3
+    assert 0.5 * G.LONG_F32_MEASURED <= err[~flipped].max() <= G.LONG_F32_MEASURED
+    assert G.LONG_F32_BOUND == 4 * G.LONG_F32_MEASURED
+    for dtype in (torch.float32, f64):
+        acc = run.oracle(dtype)[1]["acc_rate"].mean()
+        assert 0.5 <= acc <= 1.0, acc
