@@ -14,6 +14,11 @@
 #define HTA_CB_SET_SPLIT 4  /* hta_cb_split_kernel: split HMC on a LIST of callables          */
 #define HTA_CB_SET_PATH 5   /* hta_cb_path_kernel | hta_cb_split_path_kernel (info[6] = M | 0): leapfrog paths */
 #define HTA_CB_SET_ROLLED 6 /* hta_cb_rolled_kernel: plain HMC on a callable rolled over its data rows (info[6] = U, info[7] = groups) */
+#define HTA_CB_SET_RMHMC_HESS 7 /* hta_cb_rmhmc_hess_kernel: explicit RMHMC trajectories with Metric.HESSIAN, D <= 16 (HtaCbRmhmcArgs, alpha unread) */
+
+/* HTA_CB_METRIC of a generated include made for an RMHMC trajectory kernel: the values of HTA_METRIC_* in include/hamiltorch_amd.h */
+#define HTA_CB_METRIC_HESSIAN 0
+#define HTA_CB_METRIC_SOFTABS 1
 
 #define HTA_CB_MAX_GROUPS 4       /* rolled groups of one callable (HtaCbRolledArgs::table / rows)                         */
 #define HTA_CB_ROLLED_LDS 65536   /* bytes of dynamic LDS of one workgroup of hta_cb_rolled_kernel at most                  */

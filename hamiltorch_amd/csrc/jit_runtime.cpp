@@ -67,7 +67,7 @@ thread_local std::string g_jit_log;
 struct Module {
   hipModule_t mod = nullptr;
   hipFunction_t hmc = nullptr, predraw = nullptr, derivs = nullptr, contract = nullptr, rmhmc = nullptr, split = nullptr, path = nullptr,
-                rolled = nullptr;
+                rolled = nullptr;       // (rmhmc: hta_cb_rmhmc_kernel or hta_cb_rmhmc_hess_kernel, by info[4])
   int rolled_max_threads = 0;       // the launch bound hta_cb_rolled_kernel was built with
   int info[HTA_CB_INFO_WORDS] = {};
   int device = -1;
@@ -114,6 +114,7 @@ const struct KernelSet {
     {HTA_CB_SET_SPLIT, "hta_cb_split_kernel", &Module::split, nullptr, nullptr},
     {HTA_CB_SET_PATH, "hta_cb_path_kernel", &Module::path, nullptr, nullptr},          // a list (info[6] = M > 0): hta_cb_split_path_kernel
     {HTA_CB_SET_ROLLED, "hta_cb_rolled_kernel", &Module::rolled, "hta_cb_predraw_kernel", &Module::predraw},
+    {HTA_CB_SET_RMHMC_HESS, "hta_cb_rmhmc_hess_kernel", &Module::rmhmc, nullptr, nullptr},
 };
 
 const char* dtype_name(int itemsize) { return itemsize == 4 ? "f32" : "f64"; }
@@ -422,11 +423,14 @@ int64_t hta_jit_rmhmc_workspace_bytes(int64_t C, int D, int itemsize) {
   return C * itemsize;                          // lp_out[C]
 }
 
+/* Explicit RMHMC trajectories on a compiled callable: the module holds the soft-abs kernel (HTA_CB_SET_RMHMC) or the Metric.HESSIAN
+ * one (HTA_CB_SET_RMHMC_HESS, args->alpha unread) - the launch is the same. */
 int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int itemsize, int has_jitter, void* workspace,
                          int64_t workspace_bytes, void* stream) {
   using namespace hta;
   Module* m = (Module*)module;
-  if (int rc = check_module(m, "hta_jit_rmhmc_sample", D, itemsize, has_jitter ? 1 : 0, HTA_CB_SET_RMHMC)) return rc;
+  const bool hess = m && m->info[4] == HTA_CB_SET_RMHMC_HESS;
+  if (int rc = check_module(m, "hta_jit_rmhmc_sample", D, itemsize, has_jitter ? 1 : 0, hess ? HTA_CB_SET_RMHMC_HESS : HTA_CB_SET_RMHMC)) return rc;
   HTA_REQUIRE(args && args->cur && args->init && args->reject_count && args->C > 0 && args->L >= 0 && args->n_traj >= 0,
               "hta_jit_rmhmc_sample: bad arguments");
   HTA_REQUIRE(workspace && workspace_bytes >= hta_jit_rmhmc_workspace_bytes(args->C, D, itemsize),
@@ -435,7 +439,10 @@ int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int it
   if (args->n_traj == 0) return HTA_OK;
   HtaCbRmhmcArgs a = *args;
   a.lp_out = workspace;
-  note_route("hta_cb_rmhmc_kernel<D=%d,%s,jitter=%d,nodes=%d+%d>", D, dtype_name(itemsize), has_jitter ? 1 : 0, m->info[5], m->info[6]);
+  if (hess)
+    note_route("hta_cb_rmhmc_hess_kernel<D=%d,%s,jitter=%d,nodes=%d+%d>", D, dtype_name(itemsize), has_jitter ? 1 : 0, m->info[5], m->info[6]);
+  else
+    note_route("hta_cb_rmhmc_kernel<D=%d,%s,jitter=%d,nodes=%d+%d>", D, dtype_name(itemsize), has_jitter ? 1 : 0, m->info[5], m->info[6]);
   profile_begin((hipStream_t)stream);
   const int rc = launch(m->rmhmc, "hta_jit_rmhmc_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
   profile_end((hipStream_t)stream);

@@ -159,12 +159,20 @@ def compile_derivs(fn, example, dtype, fresh=False):
     return _compile(fn, example, dtype, "derivs", fresh)
 
 
-def compile_rmhmc(fn, example, dtype, jitter, fresh=False):
-    """The callable built into the explicit-RMHMC trajectory kernel (csrc/jit/rmhmc_callback.hip.in; D <= 16); raises ``Unsupported``."""
+# cache kinds of the explicit-RMHMC trajectory kernels -> (metric, jitter): the metric is part of the key, one entry (and one code object) each
+_RMHMC_KINDS = {"rmhmc": ("softabs", False), "rmhmc-jitter": ("softabs", True), "rmhmc-hess": ("hessian", False), "rmhmc-hess-jitter": ("hessian", True)}
+
+
+def compile_rmhmc(fn, example, dtype, jitter, fresh=False, metric="softabs"):
+    """The callable built into the explicit-RMHMC trajectory kernel of `metric` ("softabs": csrc/jit/rmhmc_callback.hip.in, "hessian":
+    csrc/jit/rmhmc_hess_callback.hip.in; D <= 16); raises ``Unsupported``."""
+    if metric not in runtime.RMHMC_SKELETONS:
+        raise ValueError("compile_rmhmc: metric is 'softabs' or 'hessian', got %r" % (metric,))
     if example.numel() > runtime.MAX_RMHMC_DIM:
         _note("D = %d: the chain-per-lane Riemannian kernel holds a chain's matrices in registers (D <= %d)" % (example.numel(), runtime.MAX_RMHMC_DIM))
         raise Unsupported(last_reason())
-    return _compile(fn, example, dtype, "rmhmc-jitter" if jitter else "rmhmc", fresh)
+    kind = next(k for k, v in _RMHMC_KINDS.items() if v == (metric, bool(jitter)))
+    return _compile(fn, example, dtype, kind, fresh)
 
 
 def compile_path(fn_or_list, example, dtype, mass_kind, fresh=False):
@@ -215,13 +223,14 @@ def _compile(fn, example, dtype, mass_kind, fresh, path=False):
     try:
         traced = trace_callback(fn, example)
         stats["traced"] += 1
-        if mass_kind in ("derivs", "rmhmc", "rmhmc-jitter"):
+        if mass_kind == "derivs" or mass_kind in _RMHMC_KINDS:
             _too_large_unrolled(traced, runtime.MAX_DERIV_NODES, "the derivative and RMHMC kernels")
             _check_against_autograd(traced, fn, example)
             if mass_kind == "derivs":
                 out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype), runtime.SKELETON_DERIVS, dtype, mass_kind)
             else:
-                out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype, mass_kind == "rmhmc-jitter"), runtime.SKELETON_RMHMC,
+                metric, jitter = _RMHMC_KINDS[mass_kind]
+                out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype, jitter, metric), runtime.RMHMC_SKELETONS[metric],
                                      dtype, mass_kind)
         else:
             out = _hmc_or_rolled(traced, fn, example, dtype, mass_kind, path)

@@ -27,6 +27,7 @@ SKELETON_PATH = "jit/path_callback.hip.in"
 SKELETON_ROLLED = "jit/rolled_callback.hip.in"
 SKELETON_DERIVS = "jit/derivs_callback.hip.in"
 SKELETON_RMHMC = "jit/rmhmc_callback.hip.in"
+SKELETON_RMHMC_HESS = "jit/rmhmc_hess_callback.hip.in"
 # (SLP vectorisation ON: the straight-line callback code packs into v_pk_mul / v_pk_fma pairs - 67 -> 59 instructions per
 #  leapfrog step of the notebook funnel, tools/jit_isa.py; -ffp-contract=fast fuses across the generated statements)
 OPTIONS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast")
@@ -372,12 +373,14 @@ MAX_DERIV_DIM = 32
 MAX_DERIV_NODES = 20000         # live scalar operations of each generated function
 
 
-MAX_RMHMC_DIM = 16              # a chain's matrices in one lane's registers (csrc/jit/rmhmc_callback.hip.in)
+MAX_RMHMC_DIM = 16              # a chain's matrices in one lane's registers (csrc/jit/rmhmc_callback.hip.in, rmhmc_hess_callback.hip.in)
+RMHMC_SKELETONS = {"softabs": SKELETON_RMHMC, "hessian": SKELETON_RMHMC_HESS}
 
 
-def derivs_generated_source(traced, dtype, jitter=False):
+def derivs_generated_source(traced, dtype, jitter=False, metric=None):
     """Value, gradient, Hessian (D reverse passes over the gradient's graph) and the third derivatives (one pass per Hessian
-    entry of the lower triangle) of a traced callable, as the generated include of csrc/jit/derivs_callback.hip.in."""
+    entry of the lower triangle) of a traced callable, as the generated include of csrc/jit/derivs_callback.hip.in - and, with
+    `metric` ("softabs" | "hessian"), of the RMHMC trajectory skeleton of that metric (RMHMC_SKELETONS)."""
     D = traced.D
     if D > MAX_DERIV_DIM:
         raise Unsupported("D = %d: third derivatives are generated entry by entry (D <= %d)" % (D, MAX_DERIV_DIM))
@@ -386,6 +389,25 @@ def derivs_generated_source(traced, dtype, jitter=False):
     hess = [g.grad(gi) for gi in grads]
     if len(g.reachable([traced.value] + grads + [hess[i][j] for i in range(D) for j in range(i + 1)])) > MAX_DERIV_NODES:
         raise Unsupported("value + gradient + Hessian exceed %d scalar operations" % MAX_DERIV_NODES)
+    # Two forms of the third derivatives behind third_contract.  Entry by entry (one reverse pass per Hessian entry), a likelihood of R
+    # terms costs R operations for each of the D^2 (D + 1) / 2 derivatives; the contraction they are wanted for is ONE scalar,
+    # s = <Hessian(theta), M>, whose gradient by reverse mode costs a few times the Hessian itself.  The Metric.HESSIAN kernel takes
+    # the second form; everything that compiled before it existed keeps the first - and its text - and either is the other's
+    # fall-back where one is refused for its size.
+    forms = (_contracted_third, _entrywise_third) if metric == "hessian" else (_entrywise_third, _contracted_third)
+    try:
+        third = forms[0](g, hess)
+    except Unsupported as e:
+        try:
+            third = forms[1](g, hess)
+        except Unsupported as e2:
+            raise Unsupported("%s; %s" % ((e, e2) if forms[0] is _entrywise_third else (e2, e))) from None
+    return emit.derivs_source(g, traced.value, grads, hess, third, dtype_name(dtype), jitter, metric)
+
+
+def _entrywise_third(g, hess):
+    """{(i, j), j <= i: the D derivatives of Hessian entry i, j}."""
+    D = g.n_inputs
     third = {}
     for i in range(D):
         for j in range(i + 1):
@@ -394,7 +416,26 @@ def derivs_generated_source(traced, dtype, jitter=False):
                 raise Unsupported("the third derivatives exceed the graph size limit")
     if len(g.reachable([t for v in third.values() for t in v])) > MAX_DERIV_NODES:
         raise Unsupported("the third derivatives exceed %d scalar operations" % MAX_DERIV_NODES)
-    return emit.derivs_source(g, traced.value, grads, hess, third, dtype_name(dtype), jitter)
+    return third
+
+
+def contracted_third(g, hess):
+    """c_k = d_k sum_{i >= j} H_ij(theta) m_ij with the m_ij held fixed, as D nodes of `g`: m_ij enters as the EXTRA input
+    D + i (i + 1) / 2 + j of the graph (emit.derivs_source fills it with M_ii, or M_ij + M_ji for an off-diagonal pair)."""
+    D = g.n_inputs
+    s = g.const(0.0)
+    for i in range(D):
+        for j in range(i + 1):
+            s = g.add(s, g.mul(hess[i][j], g._new(("in", D + i * (i + 1) // 2 + j))))
+    return g.grad(s)
+
+
+def _contracted_third(g, hess):
+    third = contracted_third(g, hess)
+    live = len(g.reachable(third))
+    if live > MAX_DERIV_NODES:
+        raise Unsupported("the gradient of the contraction <Hessian, M> exceeds %d scalar operations (%d)" % (MAX_DERIV_NODES, live))
+    return third
 
 
 def rmhmc_workspace_bytes(C, D, itemsize):
@@ -403,14 +444,15 @@ def rmhmc_workspace_bytes(C, D, itemsize):
 
 def rmhmc_sample(module, cur, init, L, eps, alpha, jitter, omega, n_traj, traj_offset, burn, seed, chain_offset, samples,
                  reject_count, workspace):
-    """hta_jit_rmhmc_sample: explicit soft-abs RMHMC trajectories [traj_offset, traj_offset + n_traj) on the compiled callable."""
+    """hta_jit_rmhmc_sample: explicit RMHMC trajectories [traj_offset, traj_offset + n_traj) on the compiled callable, under the metric
+    the module was built for (soft-abs, or Metric.HESSIAN: `alpha` is not read and may be None)."""
     _abi.require_device(cur, "params")
     C, D = cur.shape
     a = _abi.HtaCbRmhmcArgs()
     a.cur, a.init = cur.data_ptr(), _abi._p(init, cur).value
     a.samples = None if samples is None else _abi._p(samples, cur).value
     a.reject_count = reject_count.data_ptr()
-    a.C, a.eps, a.alpha, a.omega = C, float(eps), float(alpha), float(omega)
+    a.C, a.eps, a.alpha, a.omega = C, float(eps), 0.0 if alpha is None else float(alpha), float(omega)
     a.jitter = 0.0 if jitter is None else float(jitter)
     a.seed, a.chain_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_offset)
     a.L, a.n_traj, a.traj_offset, a.burn = int(L), int(n_traj), int(traj_offset), int(burn)

@@ -401,16 +401,19 @@ def explicit_leapfrog(params, momentum, log_prob_func, steps, step_size, jitter,
 
 
 def sample_explicit(log_prob_func, theta0, N, L, eps, burn, jitter, softabs_const, omega, metric, seed, chain_offset,
-                    verbose):
-    """The RMHMC / EXPLICIT branch of sample() (S:969-1026): one C call enqueues the whole run."""
+                    verbose, native=True):
+    """The RMHMC / EXPLICIT branch of sample() (S:969-1026): one C call enqueues the whole run.  native=False (like
+    HAMILTORCH_AMD_JIT=0) keeps a general callable on the launch-per-evaluation sequence."""
     from .samplers import _num_rows
     tgt = as_gaussian(log_prob_func, theta0)
     kind = _metric_kind(metric)
     if softabs_const is None and kind == _abi.METRIC_SOFTABS:
         raise TypeError("softabs_const must be set for Metric.SOFTABS")
     if tgt is None:
-        out = _sample_explicit_compiled(log_prob_func, theta0, N, L, eps, burn, jitter, softabs_const, omega, kind, seed,
-                                        chain_offset, verbose)
+        out = None
+        if native:
+            out = _sample_explicit_compiled(log_prob_func, theta0, N, L, eps, burn, jitter, softabs_const, omega, kind, seed,
+                                            chain_offset, verbose)
         if out is not None:
             return out
         return _sample_explicit_generic(log_prob_func, theta0, N, L, eps, burn, jitter, softabs_const, omega, kind, seed,
@@ -468,18 +471,20 @@ def _prepared_workspace(tgt, theta0, kind, alpha, jitter, N):
 
 
 def _sample_explicit_compiled(log_prob_func, theta0, N, L, eps, burn, jitter, alpha, omega, kind, seed, chain_offset, verbose):
-    """The whole run inside the compiled chain-per-lane kernel (hamiltorch_amd/jit/, csrc/jit/rmhmc_callback.hip.in) when the callback
-    compiler covers the callable: soft-abs metric, D <= 16.  None = not applicable (the reason is in hta_last_route()); the result is
-    checked against the callable itself on the states the run ended in, a mismatch re-traces once and else returns None."""
+    """The whole run inside a compiled chain-per-lane kernel (hamiltorch_amd/jit/; csrc/jit/rmhmc_callback.hip.in for the soft-abs metric,
+    csrc/jit/rmhmc_hess_callback.hip.in for Metric.HESSIAN, where `alpha` may be None) when the callback compiler covers the callable:
+    D <= 16.  None = not applicable (the reason is in hta_last_route()); the result is checked against the callable itself on the states
+    the run ended in, a mismatch re-traces once and else returns None."""
     from . import jit
     from .samplers import _num_rows
     C, D = theta0.shape
-    if not (jit.enabled() and callable(log_prob_func) and theta0.is_cuda and kind == _abi.METRIC_SOFTABS):
+    metric = {_abi.METRIC_SOFTABS: "softabs", _abi.METRIC_HESSIAN: "hessian"}.get(kind)
+    if not (jit.enabled() and callable(log_prob_func) and theta0.is_cuda and metric is not None):
         return None
     for fresh in (False, True):
         hits = jit.stats["trace_hits"]
         try:
-            comp = jit.compile_rmhmc(log_prob_func, theta0[0], theta0.dtype, jitter is not None, fresh=fresh)
+            comp = jit.compile_rmhmc(log_prob_func, theta0[0], theta0.dtype, jitter is not None, fresh=fresh, metric=metric)
         except jit.Unsupported as e:
             _abi.load().hta_jit_note_fallback(str(e)[:140].encode("utf-8", "replace"))
             return None

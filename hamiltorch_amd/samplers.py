@@ -573,12 +573,12 @@ def sample(log_prob_func, params_init, num_samples=10, num_steps_per_sample=10, 
                     probed = None
             samples, rejected = rmhmc.sample_explicit(lp, theta0, num_samples, num_steps_per_sample,
                                                       step_size, burn_k, jitter, softabs_const,
-                                                      explicit_binding_const, metric, seed, chain_offset, verbose)
+                                                      explicit_binding_const, metric, seed, chain_offset, verbose, native)
             if probed is not None and not verify_gaussian(probed, log_prob_func, samples):
                 _probe_mismatch(log_prob_func)
                 samples, rejected = rmhmc.sample_explicit(log_prob_func, theta0, num_samples, num_steps_per_sample,
                                                           step_size, burn_k, jitter, softabs_const,
-                                                          explicit_binding_const, metric, seed, chain_offset, verbose)
+                                                          explicit_binding_const, metric, seed, chain_offset, verbose, native)
         elif sampler == Sampler.RMHMC and integrator == Integrator.IMPLICIT:
             if pass_grad is not None:
                 raise RuntimeError('Passing user-determined gradients not implemented for RMHMC')
