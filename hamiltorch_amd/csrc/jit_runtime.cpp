@@ -117,6 +117,12 @@ const struct KernelSet {
     {HTA_CB_SET_RMHMC_HESS, "hta_cb_rmhmc_hess_kernel", &Module::rmhmc, nullptr, nullptr},
 };
 
+const KernelSet* kernel_set(int set) {
+  for (const KernelSet& k : kKernelSets)
+    if (k.set == set) return &k;
+  return nullptr;
+}
+
 const char* dtype_name(int itemsize) { return itemsize == 4 ? "f32" : "f64"; }
 const char* split_name(int kind) { return kind == HTA_CB_SPLIT_RAND ? "rand" : kind == HTA_CB_SPLIT_KMID ? "kmid" : "symmetric"; }
 
@@ -250,14 +256,12 @@ int hta_jit_load(const void* code, int64_t bytes, void** module_out) {
     return HTA_ERR_INVALID;
   }
   e = hipErrorInvalidValue;
-  for (const KernelSet& k : kKernelSets) {
-    if (k.set != m->info[4]) continue;
-    const bool list_path = k.set == HTA_CB_SET_PATH && m->info[6] > 0;
-    e = hipModuleGetFunction(&(m->*k.fn), m->mod, list_path ? "hta_cb_split_path_kernel" : k.name);
-    if (e == hipSuccess && k.name2) e = hipModuleGetFunction(&(m->*k.fn2), m->mod, k.name2);
-    if (e == hipSuccess && k.set == HTA_CB_SET_ROLLED)
+  if (const KernelSet* k = kernel_set(m->info[4])) {
+    const bool list_path = k->set == HTA_CB_SET_PATH && m->info[6] > 0;
+    e = hipModuleGetFunction(&(m->*k->fn), m->mod, list_path ? "hta_cb_split_path_kernel" : k->name);
+    if (e == hipSuccess && k->name2) e = hipModuleGetFunction(&(m->*k->fn2), m->mod, k->name2);
+    if (e == hipSuccess && k->set == HTA_CB_SET_ROLLED)
       e = hipFuncGetAttribute(&m->rolled_max_threads, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, m->rolled);
-    break;
   }
   if (e != hipSuccess) {
     set_error("hta_jit_load: kernel set %d: %s", m->info[4], hipGetErrorString(e));
@@ -429,8 +433,9 @@ int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int it
                          int64_t workspace_bytes, void* stream) {
   using namespace hta;
   Module* m = (Module*)module;
-  const bool hess = m && m->info[4] == HTA_CB_SET_RMHMC_HESS;
-  if (int rc = check_module(m, "hta_jit_rmhmc_sample", D, itemsize, has_jitter ? 1 : 0, hess ? HTA_CB_SET_RMHMC_HESS : HTA_CB_SET_RMHMC)) return rc;
+  // the module's row of kKernelSets: the set check_module asks for and the kernel's name in the route (any other module: the soft-abs row)
+  const KernelSet* k = kernel_set(m && m->info[4] == HTA_CB_SET_RMHMC_HESS ? HTA_CB_SET_RMHMC_HESS : HTA_CB_SET_RMHMC);
+  if (int rc = check_module(m, "hta_jit_rmhmc_sample", D, itemsize, has_jitter ? 1 : 0, k->set)) return rc;
   HTA_REQUIRE(args && args->cur && args->init && args->reject_count && args->C > 0 && args->L >= 0 && args->n_traj >= 0,
               "hta_jit_rmhmc_sample: bad arguments");
   HTA_REQUIRE(workspace && workspace_bytes >= hta_jit_rmhmc_workspace_bytes(args->C, D, itemsize),
@@ -439,10 +444,7 @@ int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int it
   if (args->n_traj == 0) return HTA_OK;
   HtaCbRmhmcArgs a = *args;
   a.lp_out = workspace;
-  if (hess)
-    note_route("hta_cb_rmhmc_hess_kernel<D=%d,%s,jitter=%d,nodes=%d+%d>", D, dtype_name(itemsize), has_jitter ? 1 : 0, m->info[5], m->info[6]);
-  else
-    note_route("hta_cb_rmhmc_kernel<D=%d,%s,jitter=%d,nodes=%d+%d>", D, dtype_name(itemsize), has_jitter ? 1 : 0, m->info[5], m->info[6]);
+  note_route("%s<D=%d,%s,jitter=%d,nodes=%d+%d>", k->name, D, dtype_name(itemsize), has_jitter ? 1 : 0, m->info[5], m->info[6]);
   profile_begin((hipStream_t)stream);
   const int rc = launch(m->rmhmc, "hta_jit_rmhmc_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
   profile_end((hipStream_t)stream);

@@ -164,9 +164,9 @@ _RMHMC_KINDS = {"rmhmc": ("softabs", False), "rmhmc-jitter": ("softabs", True), 
 
 
 def compile_rmhmc(fn, example, dtype, jitter, fresh=False, metric="softabs"):
-    """The callable built into the explicit-RMHMC trajectory kernel of `metric` ("softabs": csrc/jit/rmhmc_callback.hip.in, "hessian":
-    csrc/jit/rmhmc_hess_callback.hip.in; D <= 16); raises ``Unsupported``."""
-    if metric not in runtime.RMHMC_SKELETONS:
+    """The callable built into the explicit-RMHMC trajectory kernel (csrc/jit/rmhmc_callback.hip.in; D <= 16) under `metric`
+    ("softabs": rmhmc_metric_softabs.inc, "hessian": rmhmc_metric_hessian.inc); raises ``Unsupported``."""
+    if (metric, bool(jitter)) not in _RMHMC_KINDS.values():
         raise ValueError("compile_rmhmc: metric is 'softabs' or 'hessian', got %r" % (metric,))
     if example.numel() > runtime.MAX_RMHMC_DIM:
         _note("D = %d: the chain-per-lane Riemannian kernel holds a chain's matrices in registers (D <= %d)" % (example.numel(), runtime.MAX_RMHMC_DIM))
@@ -230,8 +230,7 @@ def _compile(fn, example, dtype, mass_kind, fresh, path=False):
                 out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype), runtime.SKELETON_DERIVS, dtype, mass_kind)
             else:
                 metric, jitter = _RMHMC_KINDS[mass_kind]
-                out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype, jitter, metric), runtime.RMHMC_SKELETONS[metric],
-                                     dtype, mass_kind)
+                out = CompiledDerivs(traced, runtime.derivs_generated_source(traced, dtype, jitter, metric), runtime.SKELETON_RMHMC, dtype, mass_kind)
         else:
             out = _hmc_or_rolled(traced, fn, example, dtype, mass_kind, path)
         try:

@@ -20,14 +20,14 @@ from .ir import Unsupported
 _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 _HEADERS = (("cb_math.hpp", "jit/cb_math.hpp"), ("philox.hpp", "philox.hpp"), ("mh_rules.hpp", "mh_rules.hpp"),
             ("jit_args.h", "jit/jit_args.h"), ("cb_hmc_shared.hpp", "jit/cb_hmc_shared.hpp"),
-            ("cb_hmc_bodies.inc", "jit/cb_hmc_bodies.inc"))
+            ("cb_hmc_bodies.inc", "jit/cb_hmc_bodies.inc"),
+            ("rmhmc_metric_softabs.inc", "jit/rmhmc_metric_softabs.inc"), ("rmhmc_metric_hessian.inc", "jit/rmhmc_metric_hessian.inc"))
 SKELETON_HMC = "jit/hmc_callback.hip.in"
 SKELETON_SPLIT = "jit/split_callback.hip.in"
 SKELETON_PATH = "jit/path_callback.hip.in"
 SKELETON_ROLLED = "jit/rolled_callback.hip.in"
 SKELETON_DERIVS = "jit/derivs_callback.hip.in"
-SKELETON_RMHMC = "jit/rmhmc_callback.hip.in"
-SKELETON_RMHMC_HESS = "jit/rmhmc_hess_callback.hip.in"
+SKELETON_RMHMC = "jit/rmhmc_callback.hip.in"      # both metrics: HTA_CB_METRIC of the generated include picks rmhmc_metric_*.inc
 # (SLP vectorisation ON: the straight-line callback code packs into v_pk_mul / v_pk_fma pairs - 67 -> 59 instructions per
 #  leapfrog step of the notebook funnel, tools/jit_isa.py; -ffp-contract=fast fuses across the generated statements)
 OPTIONS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast")
@@ -373,14 +373,14 @@ MAX_DERIV_DIM = 32
 MAX_DERIV_NODES = 20000         # live scalar operations of each generated function
 
 
-MAX_RMHMC_DIM = 16              # a chain's matrices in one lane's registers (csrc/jit/rmhmc_callback.hip.in, rmhmc_hess_callback.hip.in)
-RMHMC_SKELETONS = {"softabs": SKELETON_RMHMC, "hessian": SKELETON_RMHMC_HESS}
+MAX_RMHMC_DIM = 16              # a chain's matrices in one lane's registers (csrc/jit/rmhmc_callback.hip.in)
 
 
 def derivs_generated_source(traced, dtype, jitter=False, metric=None):
     """Value, gradient, Hessian (D reverse passes over the gradient's graph) and the third derivatives (one pass per Hessian
     entry of the lower triangle) of a traced callable, as the generated include of csrc/jit/derivs_callback.hip.in - and, with
-    `metric` ("softabs" | "hessian"), of the RMHMC trajectory skeleton of that metric (RMHMC_SKELETONS)."""
+    `metric` ("softabs" | "hessian"), of the RMHMC trajectory skeleton (SKELETON_RMHMC), which takes
+    its metric from the include (none: soft-abs)."""
     D = traced.D
     if D > MAX_DERIV_DIM:
         raise Unsupported("D = %d: third derivatives are generated entry by entry (D <= %d)" % (D, MAX_DERIV_DIM))

@@ -471,8 +471,8 @@ def _prepared_workspace(tgt, theta0, kind, alpha, jitter, N):
 
 
 def _sample_explicit_compiled(log_prob_func, theta0, N, L, eps, burn, jitter, alpha, omega, kind, seed, chain_offset, verbose):
-    """The whole run inside a compiled chain-per-lane kernel (hamiltorch_amd/jit/; csrc/jit/rmhmc_callback.hip.in for the soft-abs metric,
-    csrc/jit/rmhmc_hess_callback.hip.in for Metric.HESSIAN, where `alpha` may be None) when the callback compiler covers the callable:
+    """The whole run inside a compiled chain-per-lane kernel (hamiltorch_amd/jit/; csrc/jit/rmhmc_callback.hip.in with rmhmc_metric_softabs.inc for
+    the soft-abs metric, with rmhmc_metric_hessian.inc for Metric.HESSIAN, where `alpha` may be None) when the callback compiler covers the callable:
     D <= 16.  None = not applicable (the reason is in hta_last_route()); the result is checked against the callable itself on the states
     the run ended in, a mismatch re-traces once and else returns None."""
     from . import jit

@@ -1,4 +1,4 @@
-"""GPU parity of the compiled explicit-RMHMC trajectory kernel for Metric.HESSIAN (csrc/jit/rmhmc_hess_callback.hip.in,
+"""GPU parity of the compiled explicit-RMHMC trajectory kernel for Metric.HESSIAN (csrc/jit/rmhmc_callback.hip.in with rmhmc_metric_hessian.inc,
 hta_cb_rmhmc_hess_kernel): sample(sampler=RMHMC, integrator=EXPLICIT, metric=HESSIAN) on a general log-concave callable, one chain
 per lane, against the oracle on the same Philox streams (chain by chain), against the launch-per-evaluation route of the same
 library (HAMILTORCH_AMD_JIT=0), cut into launches, on a metric that is not positive definite, and through the switches.  The route

@@ -1,7 +1,8 @@
-"""CPU half of the compiled Metric.HESSIAN trajectory kernel (csrc/jit/rmhmc_hess_callback.hip.in): the generated include and the
-skeleton build for gfx950 through hipRTC (no GPU needed), with no more scratch than the soft-abs kernel of the same callable; the metric
-is part of the cache key; the third-derivative contraction in its reverse-mode form equals the oracle's; and the oracle itself decides
-the cases of tests/test_gpu_jit_rmhmc_hessian.py in float32 as in float64, far inside the float32 band.
+"""CPU half of the compiled Metric.HESSIAN trajectory kernel (csrc/jit/rmhmc_callback.hip.in with rmhmc_metric_hessian.inc): the
+generated include and the skeleton build for gfx950 through hipRTC (no GPU needed), with no more scratch than the soft-abs kernel of the
+same callable; the metric is part of the cache key and an include that names an unknown one does not compile; the third-derivative
+contraction in its reverse-mode form equals the oracle's; and the oracle itself decides the cases of
+tests/test_gpu_jit_rmhmc_hessian.py in float32 as in float64, far inside the float32 band.
 """
 import os
 import re
@@ -63,7 +64,7 @@ def _header_constant(name):
 def built(D, dtype, jitter, metric, tmp_path):
     tr = trace_callback(logcosh_logp(*target(D)), torch.ones(D, dtype=torch.float64))
     src = runtime.derivs_generated_source(tr, dtype, jitter, metric)
-    key, blob = runtime.compile_source(src, runtime.RMHMC_SKELETONS[metric])
+    key, blob = runtime.compile_source(src, runtime.SKELETON_RMHMC)
     sym, regs = _symbols(blob, tmp_path)
     return src, blob, sym, regs
 
@@ -90,15 +91,15 @@ def test_symbols_and_resources(D, dtype, tmp_path):
 
 
 def test_the_metric_is_part_of_the_cache_key():
-    """compile_rmhmc under the two metrics: two cache entries and two code objects for one callable, each handed out again
-    without a new trace; the soft-abs include is the parent's text plus the metric define."""
+    """compile_rmhmc under the two metrics: two cache entries and two code objects of the one skeleton for one callable, each handed
+    out again without a new trace; the soft-abs include is the parent's text plus the metric define."""
     P, A = target(3)
     fn, ex = logcosh_logp(P, A), torch.ones(3, dtype=torch.float32)
     traced = jit.stats["traced"]
     soft = jit.compile_rmhmc(fn, ex, torch.float32, True)
     hess = jit.compile_rmhmc(fn, ex, torch.float32, True, metric="hessian")
     assert soft is not hess and soft.key != hess.key
-    assert (soft.skeleton, hess.skeleton) == (runtime.SKELETON_RMHMC, runtime.SKELETON_RMHMC_HESS)
+    assert soft.skeleton == hess.skeleton == runtime.SKELETON_RMHMC and soft.blob != hess.blob
     assert (soft.mass_kind, hess.mass_kind) == ("rmhmc-jitter", "rmhmc-hess-jitter")
     assert {cfg[2] for cfg in jit._by_fn[fn]} == {"rmhmc-jitter", "rmhmc-hess-jitter"}
     assert jit.compile_rmhmc(fn, ex, torch.float32, False, metric="hessian").key not in (soft.key, hess.key)
@@ -114,6 +115,19 @@ def test_the_metric_is_part_of_the_cache_key():
     with_metric = runtime.derivs_generated_source(tr, torch.float32, True, "softabs")
     assert with_metric.replace("#define HTA_CB_METRIC HTA_CB_METRIC_SOFTABS\n", "") == runtime.derivs_generated_source(tr, torch.float32, True)
     assert "by reverse mode" not in with_metric
+
+
+def test_an_unknown_metric_in_the_include_does_not_compile():
+    """The skeleton takes its metric from HTA_CB_METRIC of the generated include: a value that is neither metric's is an #error whose
+    message names the accepted ones - and so is a name that is no macro at all, which the preprocessor alone would read as 0."""
+    tr = trace_callback(logcosh_logp(*target(2)), torch.ones(2, dtype=torch.float64))
+    src = runtime.derivs_generated_source(tr, torch.float32, True, "hessian")
+    line = "#define HTA_CB_METRIC HTA_CB_METRIC_HESSIAN\n"
+    assert src.count(line) == 1
+    for value in ("7", "HTA_CB_METRIC_FISHER"):
+        with pytest.raises(runtime.CompileError) as e:
+            runtime.compile_source(src.replace(line, "#define HTA_CB_METRIC %s\n" % value), runtime.SKELETON_RMHMC)
+        assert "HTA_CB_METRIC_SOFTABS" in e.value.log and "HTA_CB_METRIC_HESSIAN" in e.value.log, e.value.log
 
 
 @pytest.mark.parametrize("D", [2, 5, 11, 16])

@@ -97,7 +97,7 @@ def resources():
 
     def counts(Dk, dtype, jitter, metric):
         tr = trace_callback(logcosh(Dk), torch.ones(Dk, dtype=torch.float64))
-        _, blob = runtime.compile_source(runtime.derivs_generated_source(tr, dtype, jitter, metric), runtime.RMHMC_SKELETONS[metric])
+        _, blob = runtime.compile_source(runtime.derivs_generated_source(tr, dtype, jitter, metric), runtime.SKELETON_RMHMC)
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(blob); f.flush()
             notes = subprocess.run([READELF, "--notes", f.name], capture_output=True, text=True).stdout
