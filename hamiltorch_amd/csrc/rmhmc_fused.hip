@@ -24,20 +24,19 @@
 #include "philox.hpp"
 #include "rmhmc.hpp"
 #include "rmhmc_fused_dev.hpp"
+#include "rmhmc_rows4_dev.hpp"
 
 #ifndef HTA_RM_TIMING
-#define HTA_RM_TIMING 0   // developer cycle counters (thread 0 of block 0): tools/scratch/rmhmc_time.py prints them
+#define HTA_RM_TIMING 0   // developer cycle counters of the one-chain kernel (thread 0 of block 0; build with -DHTA_RM_TIMING=1): tools/scratch/rmhmc_time.py prints them
 #endif
 #if HTA_RM_TIMING
-__device__ unsigned long long hta_rm_dbg[16];
+__device__ unsigned long long hta_rm_dbg[8];
 extern "C" void hta_rm_dbg_read(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(hta_rm_dbg), sizeof(hta_rm_dbg)); }
-#define HTA_XTICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); xacc[k] += now_ - xlast; xlast = now_; } while (0)
 #define HTA_RTICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); ch.tacc[0] += now_ - ch.tlast; ch.tlast = now_; } while (0)
 #define HTA_MTICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[k] += now_ - tlast; tlast = now_; } while (0)
 #else
 #define HTA_RTICK(k) do {} while (0)
 #define HTA_MTICK(k) do {} while (0)
-#define HTA_XTICK(k) do {} while (0)
 #endif
 
 namespace hta {
@@ -385,7 +384,7 @@ template <typename T, int KH, int NC, bool TRACK = false> struct Fused {
     HTA_MTICK(3);
   }
 
-  // ---- TRACK: the half steps without their P d and S m products (the schedule and its derivation: rmhmc_mfma4x4_kernel) ----
+  // ---- TRACK: the half steps without their P d and S m products (the schedule and its derivation: rows4_trajectories) ----
   // Up to two P products and two S products with ONE pass over the slices: op_i = P vp_i, os_i = S vs_i, complete in both
   // lanes of the row.  Per product the chunks and the order of the sum are those of products().
   template <int NPV, int NSV>
@@ -762,66 +761,66 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_num_vgpr(HTA_FUSED_WIDE_
 // D = 100) and by its pass latency (7 row tiles on 4 SIMDs: 2 x 56 MFMAs x 32 clk per first pass): measured against one chain
 // per workgroup 0.6x / 0.96x / 1.19x / 1.37x at 512 / 1024 / 2048 / 4096 chains (tools/scratch/pair_check.py), so it is taken
 // from 2048 chains per GPU on (hta_set_tuning("rmhmc_batch", 0) off, 2 always); there the per-trajectory Cholesky of the
-// momentum draw is the next limit.  TRACK ("rmhmc_pair" = 1, the default): the tracked-products schedule derived at
-// rmhmc_mfma4x4_kernel (4096 chains: 1.56e8 -> 1.84e8 steps/s, 3072: 1.24e8 -> 1.47e8).
+// momentum draw is the next limit.  TRACK ("rmhmc_pair" = 1, the default): the tracked-products schedule derived in
+// rows4_trajectories (4096 chains: 1.56e8 -> 1.84e8 steps/s, 3072: 1.24e8 -> 1.47e8).
+// The algorithm is rows4_trajectories (rmhmc_rows4_dev.hpp); BatchTile is this kernel's layout and its products.
 // =============================================================================================
 constexpr int BNC = 16, BLD = 116, BWV = 7, BNT = 64 * BWV, BSEG = 28, BBUF = 12;
 
 // BKJ: MFMAs per product and row tile = K / 4 (25 for D <= 100, 28 up to 112).  A vector is stored in four segments of BSEG
 // floats (16-byte aligned); element `row` sits in segment row / BKJ at offset row % BKJ.
-template <int BKJ, bool TRACK>
-__global__ __launch_bounds__(BNT) void rmhmc_batch_kernel(FusedArgs<float> a) {
+template <int BKJ>
+struct BatchTile {
   typedef float T;
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* lds = reinterpret_cast<T*>(smem_raw);
-  constexpr int MSZ = BNC * BLD;
-  T* PM = lds; T* PMC = PM + MSZ; T* D1 = PMC + MSZ;
-  T* DC = D1 + MSZ;                                       // tracked products: theta_c - mu (D1: theta - mu)
-  T* D0 = DC + MSZ; T* W0 = D0 + MSZ; T* W1 = W0 + MSZ; T* EV = W1 + MSZ;
-  // tracked products: 2 pairs x 2 solves x 2 refinement vectors.  The first pair's four ARE the Hamiltonians' D0 W0 W1 EV
-  // (contiguous): a Hamiltonian and the first pair of a step are always separated by barriers (block_sums / the solve phases of
-  // the second pair), and the whole set stays at 12 matrices = 88 KB
-  T* WS2 = EV + MSZ;
-  T* red = WS2 + 4 * MSZ;                                 // [BWV][BNC][4]
-  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, cl = l & 15, g = l >> 4;
-  const int D = a.D;
-  const int row0 = 16 * w + 4 * g, arow = 16 * w + cl;
-  T Sa[BKJ], Pa[BKJ];
-#pragma unroll
-  for (int j = 0; j < BKJ; ++j) {
-    const int k = BKJ * g + j;
-    const bool ok = arow < D && k < D;
-    Sa[j] = ok ? a.S[(int64_t)k * D + arow] : 0.f;        // symmetric: column arow, coalesced over the lanes of a tile
-    Pa[j] = ok ? a.P[(int64_t)k * D + arow] : 0.f;
-  }
-  T mu_r[4], sd_r[4];
-  bool rok[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int r = row0 + e;
-    rok[e] = r < D;
-    mu_r[e] = rok[e] ? a.mu[r] : 0.f;
-    sd_r[e] = rok[e] ? a.S[(int64_t)r * D + r] : 0.f;
-  }
-  for (int e = tid; e < BBUF * MSZ + BWV * BNC * 4; e += BNT) lds[e] = 0.f;
-  const T eh = 0.5f * a.eps;
-  int own_pos[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) own_pos[e] = cl * BLD + ((row0 + e) / BKJ) * BSEG + (row0 + e) % BKJ;
-  const int b_off = cl * BLD + BSEG * g;
-  int dpar = 0;
-  T ev_r[4] = {0.f, 0.f, 0.f, 0.f};
-  uint64_t chain = 0;
-  bool live = false;
+  static constexpr int NC = BNC, MSZ = BNC * BLD;
+  T *PM, *PMC, *D1, *DC, *D0, *W0, *W1, *EV, *WSA, *WSB, *red;
+  int row0, cl, w, g, b_off, own_pos[4];
+  bool rok[4], writer;
+  T mu_r[4], sd_r[4], Sa[BKJ], Pa[BKJ];
 
-  auto put4 = [&](T* X, const T (&v)[4]) {
+  __device__ __forceinline__ BatchTile(const FusedArgs<float>& a, T* lds) {
+    PM = lds; PMC = PM + MSZ; D1 = PMC + MSZ;
+    DC = D1 + MSZ;                                        // tracked products: theta_c - mu (D1: theta - mu)
+    D0 = DC + MSZ; W0 = D0 + MSZ; W1 = W0 + MSZ; EV = W1 + MSZ;
+    // tracked products: 2 pairs x 2 solves x 2 refinement vectors.  The first pair's four ARE the Hamiltonians' D0 W0 W1 EV
+    // (contiguous): a Hamiltonian and the first pair of a step are always separated by barriers (block_sums / the solve phases of
+    // the second pair), and the whole set stays at 12 matrices = 88 KB
+    WSA = D0; WSB = EV + MSZ;
+    red = WSB + 4 * MSZ;                                  // [BWV][BNC][4]
+    const int tid = threadIdx.x, l = tid & 63;
+    w = tid >> 6; cl = l & 15; g = l >> 4;
+    const int D = a.D;
+    row0 = 16 * w + 4 * g;
+    const int arow = 16 * w + cl;
+    writer = w == 0 && g == 0;
+#pragma unroll
+    for (int j = 0; j < BKJ; ++j) {
+      const int k = BKJ * g + j;
+      const bool ok = arow < D && k < D;
+      Sa[j] = ok ? a.S[(int64_t)k * D + arow] : 0.f;      // symmetric: column arow, coalesced over the lanes of a tile
+      Pa[j] = ok ? a.P[(int64_t)k * D + arow] : 0.f;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int r = row0 + e;
+      rok[e] = r < D;
+      mu_r[e] = rok[e] ? a.mu[r] : 0.f;
+      sd_r[e] = rok[e] ? a.S[(int64_t)r * D + r] : 0.f;
+    }
+    for (int e = tid; e < BBUF * MSZ + BWV * BNC * 4; e += BNT) lds[e] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) own_pos[e] = cl * BLD + ((row0 + e) / BKJ) * BSEG + (row0 + e) % BKJ;
+    b_off = cl * BLD + BSEG * g;
+  }
+
+  __device__ __forceinline__ void put4(T* X, const T (&v)[4]) const {
     if constexpr (BKJ == BSEG) *reinterpret_cast<bf4*>(X + own_pos[0]) = bf4{v[0], v[1], v[2], v[3]};
     else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) if (rok[e]) X[own_pos[e]] = v[e];     // rows >= D have no slot in this layout (and stay 0)
     }
-  };
-  auto load_b = [&](const T* X, T (&b)[BKJ]) {
+  }
+  __device__ __forceinline__ void load_b(const T* X, T (&b)[BKJ]) const {
 #pragma unroll
     for (int q = 0; q < BKJ / 4; ++q) {
       const bf4 v = *reinterpret_cast<const bf4*>(X + b_off + 4 * q);
@@ -829,158 +828,36 @@ __global__ __launch_bounds__(BNT) void rmhmc_batch_kernel(FusedArgs<float> a) {
     }
 #pragma unroll
     for (int j = (BKJ / 4) * 4; j < BKJ; ++j) b[j] = X[b_off + j];
-  };
-  auto jitter4 = [&](uint32_t n, uint32_t sub) {            // this lane's four rows are one Philox block (uniform_elem layout)
-    if (!a.has_jitter) return;
-    const U4 r = philox_block(a.seed, chain, n, PURPOSE_JITTER, sub, (uint32_t)(row0 >> 2));
-    const T u[4] = {u23<T>(r.x), u23<T>(r.y), u23<T>(r.z), u23<T>(r.w)};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ev_r[e] = (live && rok[e]) ? a.jitter * u[e] : 0.f;
-  };
-  // x = (P + diag(e))^-1 m continued from x0 = S m (rmhmc_fused_kernel: refine)
-  auto refine = [&](const T (&x0)[4], T (&xr)[4]) {
-    for (int it = 0; it < a.K; ++it) {
-      const T* wr = (it & 1) ? W1 : W0;
-      T* ww = (it & 1) ? W0 : W1;
-      __syncthreads();
-      T bw[BKJ];
-      load_b(wr, bw);
-      bf4 sx = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < BKJ; ++j) sx = __builtin_amdgcn_mfma_f32_16x16x4f32(Sa[j], bw[j], sx, 0, 0, 0);
-      T wv[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { xr[e] = x0[e] - sx[e]; wv[e] = ev_r[e] * xr[e]; }
-      put4(ww, wv);
-    }
-  };
-  // one half step: upd_x += eh G(X)^-1 m ; upd_g -= eh P (X - mu)   (rmhmc_fused_kernel: half_step)
-  auto half_step = [&](uint32_t n, uint32_t sub, const T (&X)[4], const T* m, T (&upd_x)[4], T (&upd_g)[4], T* upd_g_lds) {
-    T* d = dpar ? D1 : D0;
-    dpar ^= 1;
-    T dv[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) dv[e] = rok[e] ? X[e] - mu_r[e] : 0.f;
-    put4(d, dv);
-    __syncthreads();
-    T bd[BKJ], bm[BKJ];
-    load_b(d, bd);
-    load_b(m, bm);
-    bf4 Pd = {0.f, 0.f, 0.f, 0.f}, x0v = {0.f, 0.f, 0.f, 0.f};
+  }
+  __device__ __forceinline__ void prod2(const T (&A1)[BKJ], const T* X1, const T (&A2)[BKJ], const T* X2, bf4& acc1, bf4& acc2) const {
+    T b1[BKJ], b2[BKJ];
+    load_b(X1, b1);
+    load_b(X2, b2);
 #pragma unroll
     for (int j = 0; j < BKJ; ++j) {
-      Pd = __builtin_amdgcn_mfma_f32_16x16x4f32(Pa[j], bd[j], Pd, 0, 0, 0);
-      x0v = __builtin_amdgcn_mfma_f32_16x16x4f32(Sa[j], bm[j], x0v, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(A1[j], b1[j], acc1, 0, 0, 0);
+      acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(A2[j], b2[j], acc2, 0, 0, 0);
     }
-    jitter4(n, sub);            // first needed after the products: its Philox rounds issue under the MFMAs
-    T x0[4], xr[4], wv[4];
+  }
+  __device__ __forceinline__ void prod1(const T* X, bf4& acc) const {
+    T bw[BKJ];
+    load_b(X, bw);
+    acc = bf4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      upd_g[e] -= eh * Pd[e];
-      x0[e] = x0v[e]; xr[e] = x0v[e];
-      wv[e] = ev_r[e] * x0v[e];
-    }
-    put4(upd_g_lds, upd_g);
-    put4(W0, wv);
-    refine(x0, xr);
+    for (int j = 0; j < BKJ; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Sa[j], bw[j], acc, 0, 0, 0);
+  }
+  __device__ __forceinline__ void prod1_sq(const T* X, bf4& acc) const {
+    T be[BKJ];
+    load_b(X, be);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) upd_x[e] += eh * xr[e];
-  };
-  // ---- TRACK: the tracked-products schedule of rmhmc_mfma4x4_kernel (derivation there) in this kernel's layout ----------
-  T y[4], yc[4], z[4], zc[4];
-  // two independent solves x = (P + E)^-1 m from x_0 = S m, K phases; wa / wb return e . x_(K-1) (zero without jitter)
-  auto solve2 = [&](T* WB, const T (&ea)[4], const T (&eb)[4], const T (&x0a)[4], const T (&x0b)[4], T (&xa)[4], T (&xb)[4],
-                    T (&wa)[4], T (&wb)[4]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { xa[e] = x0a[e]; xb[e] = x0b[e]; wa[e] = 0.f; wb[e] = 0.f; }
-    for (int it = 0; it < a.K; ++it) {
-      T* A = WB + (it & 1) * MSZ;                           // read in this phase only; rewritten two phases later
-      T* B = A + 2 * MSZ;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { wa[e] = ea[e] * xa[e]; wb[e] = eb[e] * xb[e]; }
-      put4(A, wa);
-      put4(B, wb);
-      __syncthreads();
-      T ba[BKJ], bb[BKJ];
-      load_b(A, ba);
-      load_b(B, bb);
-      bf4 ra = {0.f, 0.f, 0.f, 0.f}, rb = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < BKJ; ++j) {
-        ra = __builtin_amdgcn_mfma_f32_16x16x4f32(Sa[j], ba[j], ra, 0, 0, 0);
-        rb = __builtin_amdgcn_mfma_f32_16x16x4f32(Sa[j], bb[j], rb, 0, 0, 0);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { xa[e] = x0a[e] - ra[e]; xb[e] = x0b[e] - rb[e]; }
-    }
-  };
-  // a pair of half steps (S:429-433 and, with the roles of the copies swapped, S:454-458):
-  //   a:  g1 -= eh P (X1 - mu)   X2 += eh (P + E_a)^-1 g2        b:  g2 -= eh P (X2 - mu)   X1 += eh (P + E_b)^-1 g1
-  // with y1 = P (X1 - mu), y2 = P (X2 - mu), z1 = S g1, z2 = S g2 kept current
-  auto pair_tracked = [&](T* WB, uint32_t n, uint32_t suba, uint32_t subb, T (&X1)[4], T (&X2)[4], T (&g1)[4], T (&g2)[4],
-                          T (&y1)[4], T (&y2)[4], T (&z1)[4], T (&z2)[4]) {
-    T ea[4], eb[4];
-    jitter4(n, suba);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ea[e] = ev_r[e];
-    jitter4(n, subb);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      eb[e] = ev_r[e];
-      g1[e] -= eh * y1[e];                                  // a's momentum update ...
-      z1[e] -= eh * (rok[e] ? X1[e] - mu_r[e] : 0.f);       // ... and S g1 with it
-    }
-    T xa[4], xb[4], wa[4], wb[4];
-    solve2(WB, ea, eb, z2, z1, xa, xb, wa, wb);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      X2[e] += eh * xa[e];                                  // a's position update; P x_a = g2 - e_a . x_a(K-1)
-      y2[e] += eh * (g2[e] - wa[e]);
-      g2[e] -= eh * y2[e];                                  // b's momentum update
-      z2[e] -= eh * (rok[e] ? X2[e] - mu_r[e] : 0.f);
-      X1[e] += eh * xb[e];                                  // b's position update
-      y1[e] += eh * (g1[e] - wb[e]);
-    }
-  };
-  // y, y_c, z, z_c of the current state, afresh: two passes of two products (four operand vectors at once do not fit the registers)
-  auto refresh_tracked = [&](const T (&th)[4], const T (&thc)[4], const T (&pm_)[4], const T (&pmc_)[4]) {
-    T dt[4], dc[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { dt[e] = rok[e] ? th[e] - mu_r[e] : 0.f; dc[e] = rok[e] ? thc[e] - mu_r[e] : 0.f; }
-    put4(D1, dt);
-    put4(DC, dc);
-    put4(PM, pm_);
-    put4(PMC, pmc_);
-    __syncthreads();
-    {
-      T b1[BKJ], b2[BKJ];
-      load_b(D1, b1);
-      load_b(DC, b2);
-      bf4 p1 = {0.f, 0.f, 0.f, 0.f}, p2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < BKJ; ++j) {
-        p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(Pa[j], b1[j], p1, 0, 0, 0);
-        p2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Pa[j], b2[j], p2, 0, 0, 0);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { y[e] = p1[e]; yc[e] = p2[e]; }
-    }
-    {
-      T b1[BKJ], b2[BKJ];
-      load_b(PM, b1);
-      load_b(PMC, b2);
-      bf4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < BKJ; ++j) {
-        s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(Sa[j], b1[j], s1, 0, 0, 0);
-        s2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Sa[j], b2[j], s2, 0, 0, 0);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { z[e] = s1[e]; zc[e] = s2[e]; }
-    }
-  };
-  // three sums per chain over the rows, complete in every lane of the chain's column
-  auto block_sums = [&](T (&v)[3]) {
+    for (int j = 0; j < BKJ; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Sa[j] * Sa[j], be[j], acc, 0, 0, 0);
+  }
+  // two passes of two products (four operand vectors at once do not fit the registers)
+  __device__ __forceinline__ void prod4(const T* X1, const T* X2, const T* X3, const T* X4, bf4& p1, bf4& p2, bf4& s3, bf4& s4) const {
+    prod2(Pa, X1, Pa, X2, p1, p2);
+    prod2(Sa, X3, Sa, X4, s3, s4);
+  }
+  __device__ __forceinline__ void block_sums(T (&v)[3]) const {
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
       v[e] += __shfl_xor(v[e], 16, 64);
@@ -999,135 +876,14 @@ __global__ __launch_bounds__(BNT) void rmhmc_batch_kernel(FusedArgs<float> a) {
       for (int i = 0; i < BWV; ++i) s += red[(i * BNC + cl) * 4 + e];
       v[e] = s;
     }
-  };
-  // H = -log p + D/2 log 2 pi + 1/2 log|G| + 1/2 m^T G^-1 m  (S:731)   (rmhmc_fused_kernel: hamiltonian, series branch)
-  auto hamiltonian = [&](uint32_t n, uint32_t sub, const T (&X)[4], const T* m, const T (&mr)[4], T& H, T& logp, T (&Pd_out)[4],
-                         T (&Sm_out)[4]) {
-    T* d = (dpar && !TRACK) ? D1 : D0;                      // (TRACK: D1 belongs to the refresh phase)
-    dpar ^= 1;
-    jitter4(n, sub);
-    T dr[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) dr[e] = rok[e] ? X[e] - mu_r[e] : 0.f;
-    put4(EV, ev_r);
-    put4(d, dr);
-    __syncthreads();
-    T bd[BKJ], bm[BKJ];
-    load_b(d, bd);
-    load_b(m, bm);
-    bf4 Pd = {0.f, 0.f, 0.f, 0.f}, x0v = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < BKJ; ++j) {
-      Pd = __builtin_amdgcn_mfma_f32_16x16x4f32(Pa[j], bd[j], Pd, 0, 0, 0);
-      x0v = __builtin_amdgcn_mfma_f32_16x16x4f32(Sa[j], bm[j], x0v, 0, 0, 0);
-    }
-    if (a.has_jitter) {                                     // second-order log-det term: (S . S) e
-      T be[BKJ];
-      load_b(EV, be);
-#pragma unroll
-      for (int j = 0; j < BKJ; ++j) s2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Sa[j] * Sa[j], be[j], s2, 0, 0, 0);
-    }
-    T v[3] = {0.f, 0.f, 0.f}, x0[4], xr[4], wv[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      x0[e] = x0v[e]; xr[e] = x0v[e];
-      Pd_out[e] = Pd[e]; Sm_out[e] = x0v[e];
-      v[0] += dr[e] * Pd[e];
-      wv[e] = ev_r[e] * x0v[e];
-      if (a.has_jitter) v[2] += ev_r[e] * (sd_r[e] - 0.5f * s2[e]);      // log|P + E| = log|P| + tr(SE) - 1/2 tr((SE)^2) + ...
-    }
-    put4(W0, wv);
-    refine(x0, xr);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[1] += mr[e] * xr[e];
-    block_sums(v);
-    const float pi_term = (float)D * 1.8378770351409912f;   // S:712
-    logp = a.log_norm - 0.5f * v[0];
-    H = -logp + 0.5f * pi_term + 0.5f * (a.logdetP + v[2]) + 0.5f * v[1];
-  };
-
-  const int64_t ngroup = (a.C + BNC - 1) / BNC;
-  for (int64_t cg = blockIdx.x; cg < ngroup; cg += gridDim.x) {
-    const int64_t c = BNC * cg + cl;
-    live = c < a.C;
-    chain = a.chain_offset + (uint64_t)(live ? c : 0);
-    T scur[4], sth[4], spm[4], sthc[4], spmc[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) scur[e] = (live && rok[e]) ? a.cur[c * D + row0 + e] : 0.f;
-    int32_t rejected = 0;
-    __syncthreads();                                        // the previous group's last reads of the vector matrices
-    for (int t = 0; t < a.n_traj; ++t) {
-      const uint32_t n = (uint32_t)(a.traj_offset + t);
-      // ---- gibbs: p = chol(G(theta)) z, drawn ahead by rmhmc_momentum_kernel (S:183-184)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) spm[e] = (live && rok[e]) ? a.p_ws[((int64_t)t * a.C + c) * D + row0 + e] : 0.f;
-      put4(PM, spm);
-      T H0, H1, lp0, lp1;
-      hamiltonian(n, 1, scur, PM, spm, H0, lp0, y, z);      // S:971 -> S:822
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { sth[e] = scur[e]; sthc[e] = scur[e]; spmc[e] = spm[e]; yc[e] = y[e]; zc[e] = z[e]; }   // S:425-426
-      if (!TRACK) put4(PMC, spm);
-      for (int lstep = 0; lstep < a.L; ++lstep) {           // S:427-461
-        const uint32_t k0 = 2u + 8u * (uint32_t)lstep;
-        if (TRACK) pair_tracked(D0, n, k0 + 1, k0 + 2, sth, sthc, spm, spmc, y, yc, z, zc);    // phi_A/2, phi_B/2  S:429-433
-        else {
-          half_step(n, k0 + 1, sth, PMC, sthc, spm, PM);    // phi_A/2  S:429-430
-          half_step(n, k0 + 2, sthc, PM, sth, spmc, PMC);   // phi_B/2  S:432-433
-        }
-        if (a.K == 0) __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {                       // phi_C    S:447-450, sequential (Q1)
-          T xx = sth[e], b = spm[e], xc = sthc[e], bc = spmc[e];
-          const T h = 0.5f, cc = a.rot_c, ss = a.rot_s;
-          xx = h * ((xx + xc) + cc * (xx - xc) + ss * (b - bc));
-          b = h * ((b + bc) - ss * (xx - xc) + cc * (b - bc));
-          xc = h * ((xx + xc) - cc * (xx - xc) - ss * (b - bc));
-          bc = h * ((b + bc) + ss * (xx - xc) - cc * (b - bc));
-          sth[e] = xx; spm[e] = b; sthc[e] = xc; spmc[e] = bc;
-        }
-        if (TRACK) {
-          refresh_tracked(sth, sthc, spm, spmc);
-          pair_tracked(WS2, n, k0 + 4, k0 + 7, sthc, sth, spmc, spm, yc, y, zc, z);   // phi_B/2, phi_A/2  S:454-458
-        } else {
-          put4(PM, spm);
-          put4(PMC, spmc);
-          half_step(n, k0 + 4, sthc, PM, sth, spmc, PMC);   // phi_B/2  S:454-455
-          half_step(n, k0 + 7, sth, PMC, sthc, spm, PM);    // phi_A/2  S:457-458
-        }
-      }
-      if (TRACK) {                                          // (the tracked half steps keep the momenta in registers)
-        if (a.K == 0) __syncthreads();                      // no solve phase since the refresh phase read PM
-        put4(PM, spm);
-      }
-      T unused1[4], unused2[4];
-      hamiltonian(n, 2u + 8u * (uint32_t)a.L, sth, PM, spm, H1, lp1, unused1, unused2);   // S:989 (Q4)
-      // ---- Metropolis test + bookkeeping (S:1000-1026, S:1045-1057)
-      const T u = u23<T>(philox_block(a.seed, chain, n, PURPOSE_MH, 0, 0).x);
-      const bool acc = mh_accept<T>(H0, H1, lp1, u);
-      const bool reset = (!acc) && ((int)n == a.burn + 1);  // Q2
-      if (live) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (rok[e]) {
-            const T vnew = acc ? sth[e] : (reset ? a.theta_init[c * D + row0 + e] : scur[e]);
-            scur[e] = vnew;
-            if (a.samples && (int)n > a.burn) a.samples[((int64_t)((int)n - a.burn) * a.C + c) * D + row0 + e] = vnew;
-          }
-        }
-        if (w == 0 && g == 0) {
-          if (a.H_old) a.H_old[(int64_t)t * a.C + c] = H0;
-          if (a.H_new) a.H_new[(int64_t)t * a.C + c] = H1;
-          if (a.accept) a.accept[(int64_t)t * a.C + c] = acc ? 1 : 0;
-        }
-      }
-      if (!acc) ++rejected;
-    }
-    if (live) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) if (rok[e]) a.cur[c * D + row0 + e] = scur[e];
-      if (w == 0 && g == 0) a.reject_count[c] += rejected;
-    }
   }
+};
+
+template <int BKJ, bool TRACK>
+__global__ __launch_bounds__(BNT) void rmhmc_batch_kernel(FusedArgs<float> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  BatchTile<BKJ> t(a, reinterpret_cast<float*>(smem_raw));
+  rows4_trajectories<TRACK>(a, t);
 }
 
 // =============================================================================================
@@ -1141,63 +897,56 @@ __global__ __launch_bounds__(BNT) void rmhmc_batch_kernel(FusedArgs<float> a) {
 // the launch) and X[n][k] (LDS, 16-byte reads, the same address for the 16 lanes of a chain) and receives
 // C[64w + 4b + r][n], r < 4: four consecutive rows of chain n = one Philox block of jitter, element-wise work in registers.
 // Same streams, same update order and barriers as rmhmc_batch_kernel; a product's sum runs over k = 0 .. D-1 in order.
-// TRACK ("rmhmc_pair" = 1, the default): the tracked-products schedule derived at rmhmc_mfma4x4_kernel - 12 products in 5 phases
+// TRACK ("rmhmc_pair" = 1, the default): the tracked-products schedule derived in rows4_trajectories - 12 products in 5 phases
 // per step at K = 2 instead of 16 in 8 (2048 chains: 1.36e8 -> 1.59e8 steps/s, 1536: 1.10e8 -> 1.29e8).  This kernel serves
-// 1025 .. 2048 chains per GPU, where two of its workgroups fill a CU's four SIMDs.
+// 1793 .. 2048 chains per GPU, where two of its workgroups fill a CU's four SIMDs.
+// The algorithm is rows4_trajectories (rmhmc_rows4_dev.hpp); Mfma4Tile is this kernel's layout and its products.
 // =============================================================================================
 constexpr int QNC = 4, QLD = 116, QWV = 2, QNT = 64 * QWV, QK = 100, QBUF = 16;
 
-template <bool TRACK>
-__global__ __launch_bounds__(QNT) void rmhmc_mfma4_kernel(FusedArgs<float> a) {
+struct Mfma4Tile {
   typedef float T;
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* lds = reinterpret_cast<T*>(smem_raw);
-  constexpr int MSZ = QNC * QLD;
-  T* PM = lds; T* PMC = PM + MSZ; T* D0 = PMC + MSZ; T* D1 = D0 + MSZ; T* W0 = D1 + MSZ; T* W1 = W0 + MSZ; T* EV = W1 + MSZ;
-  T* DC = EV + MSZ;                                       // tracked products: theta_c - mu (D1: theta - mu)
-  T* WS = DC + MSZ;                                       // tracked products: 2 pairs x 2 solves x 2 refinement vectors
-  T* red = WS + 8 * MSZ;                                  // [QWV][QNC][4]
-  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, cl = l & 3, blk = l >> 2;
-  const int D = a.D;
-  const int row0 = 64 * w + 4 * blk, arow = 64 * w + l;
-  T Sa[QK], Pa[QK];
-#pragma unroll
-  for (int k = 0; k < QK; ++k) {
-    const bool ok = arow < D && k < D;
-    Sa[k] = ok ? a.S[(int64_t)k * D + arow] : 0.f;        // symmetric: column arow, coalesced over the lanes
-    Pa[k] = ok ? a.P[(int64_t)k * D + arow] : 0.f;
-  }
-  T mu_r[4], sd_r[4];
-  bool rok[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int r = row0 + e;
-    rok[e] = r < D;
-    mu_r[e] = rok[e] ? a.mu[r] : 0.f;
-    sd_r[e] = rok[e] ? a.S[(int64_t)r * D + r] : 0.f;
-  }
-  for (int e = tid; e < QBUF * MSZ + QWV * QNC * 4; e += QNT) lds[e] = 0.f;
-  const T eh = 0.5f * a.eps;
-  const bool rany = row0 < QLD;                           // rows 116 .. 127 have no slot (and are >= D)
-  const int own_off = cl * QLD + row0, b_off = cl * QLD;
-  int dpar = 0;
-  T ev_r[4] = {0.f, 0.f, 0.f, 0.f};
-  uint64_t chain = 0;
-  bool live = false;
+  static constexpr int NC = QNC, MSZ = QNC * QLD;
+  T *PM, *PMC, *D0, *D1, *W0, *W1, *EV, *DC, *WSA, *WSB, *red;
+  int row0, cl, w, blk, own_off, b_off;
+  bool rok[4], writer, rany;
+  T mu_r[4], sd_r[4], Sa[QK], Pa[QK];
 
-  auto put4 = [&](T* X, const T (&v)[4]) { if (rany) *reinterpret_cast<bf4*>(X + own_off) = bf4{v[0], v[1], v[2], v[3]}; };
-  auto jitter4 = [&](uint32_t n, uint32_t sub) {            // this lane's four rows are one Philox block (uniform_elem layout)
-    if (!a.has_jitter) return;
-    const U4 r = philox_block(a.seed, chain, n, PURPOSE_JITTER, sub, (uint32_t)(row0 >> 2));
-    const T u[4] = {u23<T>(r.x), u23<T>(r.y), u23<T>(r.z), u23<T>(r.w)};
+  __device__ __forceinline__ Mfma4Tile(const FusedArgs<float>& a, T* lds) {
+    PM = lds; PMC = PM + MSZ; D0 = PMC + MSZ; D1 = D0 + MSZ; W0 = D1 + MSZ; W1 = W0 + MSZ; EV = W1 + MSZ;
+    DC = EV + MSZ;                                        // tracked products: theta_c - mu (D1: theta - mu)
+    WSA = DC + MSZ; WSB = WSA + 4 * MSZ;                  // tracked products: 2 pairs x 2 solves x 2 refinement vectors
+    red = WSA + 8 * MSZ;                                  // [QWV][QNC][4]
+    const int tid = threadIdx.x, l = tid & 63;
+    w = tid >> 6; cl = l & 3; blk = l >> 2;
+    const int D = a.D;
+    row0 = 64 * w + 4 * blk;
+    const int arow = 64 * w + l;
+    writer = w == 0 && blk == 0;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) ev_r[e] = (live && rok[e]) ? a.jitter * u[e] : 0.f;
-  };
+    for (int k = 0; k < QK; ++k) {
+      const bool ok = arow < D && k < D;
+      Sa[k] = ok ? a.S[(int64_t)k * D + arow] : 0.f;      // symmetric: column arow, coalesced over the lanes
+      Pa[k] = ok ? a.P[(int64_t)k * D + arow] : 0.f;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int r = row0 + e;
+      rok[e] = r < D;
+      mu_r[e] = rok[e] ? a.mu[r] : 0.f;
+      sd_r[e] = rok[e] ? a.S[(int64_t)r * D + r] : 0.f;
+    }
+    for (int e = tid; e < QBUF * MSZ + QWV * QNC * 4; e += QNT) lds[e] = 0.f;
+    rany = row0 < QLD;                                    // rows 116 .. 127 have no slot (and are >= D)
+    own_off = cl * QLD + row0; b_off = cl * QLD;
+  }
+
+  __device__ __forceinline__ void put4(T* X, const T (&v)[4]) const { if (rany) *reinterpret_cast<bf4*>(X + own_off) = bf4{v[0], v[1], v[2], v[3]}; }
   // One wave per SIMD: nothing else hides an LDS round trip, so the operand chunks (4 values of k per 16-byte read) are
   // fetched two chunks (16 MFMAs = 128 clocks) ahead of their use.
-  auto chunk = [&](const T* X, int q) { return *reinterpret_cast<const bf4*>(X + b_off + 4 * q); };
+  __device__ __forceinline__ bf4 chunk(const T* X, int q) const { return *reinterpret_cast<const bf4*>(X + b_off + 4 * q); }
   // two products with one pass over k: acc1 = A1 X1, acc2 = A2 X2 (two independent accumulator chains)
-  auto prod2 = [&](const T (&A1)[QK], const T* X1, const T (&A2)[QK], const T* X2, bf4& acc1, bf4& acc2) {
+  __device__ __forceinline__ void prod2(const T (&A1)[QK], const T* X1, const T (&A2)[QK], const T* X2, bf4& acc1, bf4& acc2) const {
     bf4 c1 = chunk(X1, 0), c2 = chunk(X2, 0), n1 = chunk(X1, 1), n2 = chunk(X2, 1);
 #pragma unroll
     for (int q = 0; q < QK / 4; ++q) {
@@ -1212,61 +961,43 @@ __global__ __launch_bounds__(QNT) void rmhmc_mfma4_kernel(FusedArgs<float> a) {
       __builtin_amdgcn_sched_barrier(0);
       c1 = n1; c2 = n2; n1 = f1; n2 = f2;
     }
-  };
-  // x = (P + diag(e))^-1 m continued from x0 = S m (rmhmc_fused_kernel: refine)
-  auto refine = [&](const T (&x0)[4], T (&xr)[4]) {
-    for (int it = 0; it < a.K; ++it) {
-      const T* wr = (it & 1) ? W1 : W0;
-      T* ww = (it & 1) ? W0 : W1;
-      __syncthreads();
-      bf4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};      // even / odd k: two chains keep the pipe issuing
-      bf4 c = chunk(wr, 0), n1 = chunk(wr, 1), n2 = chunk(wr, 2);
+  }
+  __device__ __forceinline__ void prod1(const T* X, bf4& acc) const {
+    bf4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};      // even / odd k: two chains keep the pipe issuing
+    bf4 c = chunk(X, 0), n1 = chunk(X, 1), n2 = chunk(X, 2);
 #pragma unroll
-      for (int q = 0; q < QK / 4; ++q) {
-        bf4 f = n2;
-        if (q + 3 < QK / 4) f = chunk(wr, q + 3);
-        __builtin_amdgcn_sched_barrier(0);
-        sa = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q], c[0], sa, 0, 0, 0);
-        sb = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q + 1], c[1], sb, 0, 0, 0);
-        sa = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q + 2], c[2], sa, 0, 0, 0);
-        sb = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q + 3], c[3], sb, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        c = n1; n1 = n2; n2 = f;
+    for (int q = 0; q < QK / 4; ++q) {
+      bf4 f = n2;
+      if (q + 3 < QK / 4) f = chunk(X, q + 3);
+      __builtin_amdgcn_sched_barrier(0);
+      sa = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q], c[0], sa, 0, 0, 0);
+      sb = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q + 1], c[1], sb, 0, 0, 0);
+      sa = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q + 2], c[2], sa, 0, 0, 0);
+      sb = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q + 3], c[3], sb, 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      c = n1; n1 = n2; n2 = f;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = sa[e] + sb[e];
+  }
+  __device__ __forceinline__ void prod1_sq(const T* X, bf4& acc) const {
+    bf4 c = chunk(X, 0), n1 = chunk(X, 1), n2 = chunk(X, 2), s2b = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < QK / 4; ++q) {
+      bf4 f = n2;
+      if (q + 3 < QK / 4) f = chunk(X, q + 3);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < 4; u += 2) {
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q + u] * Sa[4 * q + u], c[u], acc, 0, 0, 0);
+        s2b = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q + u + 1] * Sa[4 * q + u + 1], c[u + 1], s2b, 0, 0, 0);
       }
-      T wv[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { xr[e] = x0[e] - (sa[e] + sb[e]); wv[e] = ev_r[e] * xr[e]; }
-      put4(ww, wv);
+      c = n1; n1 = n2; n2 = f;
     }
-  };
-  // one half step: upd_x += eh G(X)^-1 m ; upd_g -= eh P (X - mu)   (rmhmc_fused_kernel: half_step)
-  auto half_step = [&](uint32_t n, uint32_t sub, const T (&X)[4], const T* m, T (&upd_x)[4], T (&upd_g)[4], T* upd_g_lds) {
-    T* d = dpar ? D1 : D0;
-    dpar ^= 1;
-    T dv[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) dv[e] = rok[e] ? X[e] - mu_r[e] : 0.f;
-    put4(d, dv);
-    __syncthreads();
-    bf4 Pd = {0.f, 0.f, 0.f, 0.f}, x0v = {0.f, 0.f, 0.f, 0.f};
-    prod2(Pa, d, Sa, m, Pd, x0v);
-    jitter4(n, sub);            // first needed after the products: its Philox rounds issue under the MFMAs
-    T x0[4], xr[4], wv[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      upd_g[e] -= eh * Pd[e];
-      x0[e] = x0v[e]; xr[e] = x0v[e];
-      wv[e] = ev_r[e] * x0v[e];
-    }
-    put4(upd_g_lds, upd_g);
-    put4(W0, wv);
-    refine(x0, xr);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) upd_x[e] += eh * xr[e];
-  };
-  // ---- TRACK: the tracked-products schedule of rmhmc_mfma4x4_kernel (derivation there) in this kernel's layout ----------
-  T y[4], yc[4], z[4], zc[4];
-  auto prod4 = [&](const T* X1, const T* X2, const T* X3, const T* X4, bf4& p1, bf4& p2, bf4& s3, bf4& s4) {   // P X1, P X2, S X3, S X4
+    for (int e = 0; e < 4; ++e) acc[e] += s2b[e];
+  }
+  __device__ __forceinline__ void prod4(const T* X1, const T* X2, const T* X3, const T* X4, bf4& p1, bf4& p2, bf4& s3, bf4& s4) const {
     bf4 c1 = chunk(X1, 0), c2 = chunk(X2, 0), c3 = chunk(X3, 0), c4 = chunk(X4, 0);
 #pragma unroll
     for (int q = 0; q < QK / 4; ++q) {
@@ -1283,56 +1014,8 @@ __global__ __launch_bounds__(QNT) void rmhmc_mfma4_kernel(FusedArgs<float> a) {
       __builtin_amdgcn_sched_barrier(0);
       c1 = n1; c2 = n2; c3 = n3; c4 = n4;
     }
-  };
-  // two independent solves x = (P + E)^-1 m from x_0 = S m, K phases; wa / wb return e . x_(K-1) (zero without jitter)
-  auto solve2 = [&](T* WB, const T (&ea)[4], const T (&eb)[4], const T (&x0a)[4], const T (&x0b)[4], T (&xa)[4], T (&xb)[4],
-                    T (&wa)[4], T (&wb)[4]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { xa[e] = x0a[e]; xb[e] = x0b[e]; wa[e] = 0.f; wb[e] = 0.f; }
-    for (int it = 0; it < a.K; ++it) {
-      T* A = WB + (it & 1) * MSZ;                           // read in this phase only; rewritten two phases later
-      T* B = A + 2 * MSZ;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { wa[e] = ea[e] * xa[e]; wb[e] = eb[e] * xb[e]; }
-      put4(A, wa);
-      put4(B, wb);
-      __syncthreads();
-      bf4 ra = {0.f, 0.f, 0.f, 0.f}, rb = {0.f, 0.f, 0.f, 0.f};
-      prod2(Sa, A, Sa, B, ra, rb);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { xa[e] = x0a[e] - ra[e]; xb[e] = x0b[e] - rb[e]; }
-    }
-  };
-  // a pair of half steps (S:429-433 and, with the roles of the copies swapped, S:454-458):
-  //   a:  g1 -= eh P (X1 - mu)   X2 += eh (P + E_a)^-1 g2        b:  g2 -= eh P (X2 - mu)   X1 += eh (P + E_b)^-1 g1
-  // with y1 = P (X1 - mu), y2 = P (X2 - mu), z1 = S g1, z2 = S g2 kept current
-  auto pair_tracked = [&](T* WB, uint32_t n, uint32_t suba, uint32_t subb, T (&X1)[4], T (&X2)[4], T (&g1)[4], T (&g2)[4],
-                          T (&y1)[4], T (&y2)[4], T (&z1)[4], T (&z2)[4]) {
-    T ea[4], eb[4];
-    jitter4(n, suba);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ea[e] = ev_r[e];
-    jitter4(n, subb);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      eb[e] = ev_r[e];
-      g1[e] -= eh * y1[e];                                  // a's momentum update ...
-      z1[e] -= eh * (rok[e] ? X1[e] - mu_r[e] : 0.f);       // ... and S g1 with it
-    }
-    T xa[4], xb[4], wa[4], wb[4];
-    solve2(WB, ea, eb, z2, z1, xa, xb, wa, wb);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      X2[e] += eh * xa[e];                                  // a's position update; P x_a = g2 - e_a . x_a(K-1)
-      y2[e] += eh * (g2[e] - wa[e]);
-      g2[e] -= eh * y2[e];                                  // b's momentum update
-      z2[e] -= eh * (rok[e] ? X2[e] - mu_r[e] : 0.f);
-      X1[e] += eh * xb[e];                                  // b's position update
-      y1[e] += eh * (g1[e] - wb[e]);
-    }
-  };
-  // three sums per chain over the rows, complete in every lane of the chain's column
-  auto block_sums = [&](T (&v)[3]) {
+  }
+  __device__ __forceinline__ void block_sums(T (&v)[3]) const {
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
       v[e] += __shfl_xor(v[e], 4, 64);
@@ -1353,608 +1036,14 @@ __global__ __launch_bounds__(QNT) void rmhmc_mfma4_kernel(FusedArgs<float> a) {
       for (int i = 0; i < QWV; ++i) s += red[(i * QNC + cl) * 4 + e];
       v[e] = s;
     }
-  };
-  // H = -log p + D/2 log 2 pi + 1/2 log|G| + 1/2 m^T G^-1 m  (S:731)   (rmhmc_fused_kernel: hamiltonian, series branch)
-  auto hamiltonian = [&](uint32_t n, uint32_t sub, const T (&X)[4], const T* m, const T (&mr)[4], T& H, T& logp, T (&Pd_out)[4],
-                         T (&Sm_out)[4]) {
-    T* d = (dpar && !TRACK) ? D1 : D0;                      // (TRACK: D1 belongs to the refresh phase)
-    dpar ^= 1;
-    jitter4(n, sub);
-    T dr[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) dr[e] = rok[e] ? X[e] - mu_r[e] : 0.f;
-    put4(EV, ev_r);
-    put4(d, dr);
-    __syncthreads();
-    bf4 Pd = {0.f, 0.f, 0.f, 0.f}, x0v = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-    prod2(Pa, d, Sa, m, Pd, x0v);
-    if (a.has_jitter) {                                     // second-order log-det term: (S . S) e
-      bf4 c = chunk(EV, 0), n1 = chunk(EV, 1), n2 = chunk(EV, 2), s2b = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int q = 0; q < QK / 4; ++q) {
-        bf4 f = n2;
-        if (q + 3 < QK / 4) f = chunk(EV, q + 3);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < 4; u += 2) {
-          s2 = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q + u] * Sa[4 * q + u], c[u], s2, 0, 0, 0);
-          s2b = __builtin_amdgcn_mfma_f32_4x4x1f32(Sa[4 * q + u + 1] * Sa[4 * q + u + 1], c[u + 1], s2b, 0, 0, 0);
-        }
-        c = n1; n1 = n2; n2 = f;
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s2[e] += s2b[e];
-    }
-    T v[3] = {0.f, 0.f, 0.f}, x0[4], xr[4], wv[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      x0[e] = x0v[e]; xr[e] = x0v[e];
-      Pd_out[e] = Pd[e]; Sm_out[e] = x0v[e];
-      v[0] += dr[e] * Pd[e];
-      wv[e] = ev_r[e] * x0v[e];
-      if (a.has_jitter) v[2] += ev_r[e] * (sd_r[e] - 0.5f * s2[e]);      // log|P + E| = log|P| + tr(SE) - 1/2 tr((SE)^2) + ...
-    }
-    put4(W0, wv);
-    refine(x0, xr);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[1] += mr[e] * xr[e];
-    block_sums(v);
-    const float pi_term = (float)D * 1.8378770351409912f;   // S:712
-    logp = a.log_norm - 0.5f * v[0];
-    H = -logp + 0.5f * pi_term + 0.5f * (a.logdetP + v[2]) + 0.5f * v[1];
-  };
-
-  const int64_t ngroup = (a.C + QNC - 1) / QNC;
-  for (int64_t cg = blockIdx.x; cg < ngroup; cg += gridDim.x) {
-    const int64_t c = QNC * cg + cl;
-    live = c < a.C;
-    chain = a.chain_offset + (uint64_t)(live ? c : 0);
-    T scur[4], sth[4], spm[4], sthc[4], spmc[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) scur[e] = (live && rok[e]) ? a.cur[c * D + row0 + e] : 0.f;
-    int32_t rejected = 0;
-    __syncthreads();                                        // the previous group's last reads of the vector matrices
-    for (int t = 0; t < a.n_traj; ++t) {
-      const uint32_t n = (uint32_t)(a.traj_offset + t);
-      // ---- gibbs: p = chol(G(theta)) z, drawn ahead by the momentum kernel (S:183-184)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) spm[e] = (live && rok[e]) ? a.p_ws[((int64_t)t * a.C + c) * D + row0 + e] : 0.f;
-      put4(PM, spm);
-      T H0, H1, lp0, lp1;
-      hamiltonian(n, 1, scur, PM, spm, H0, lp0, y, z);      // S:971 -> S:822
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { sth[e] = scur[e]; sthc[e] = scur[e]; spmc[e] = spm[e]; yc[e] = y[e]; zc[e] = z[e]; }   // S:425-426
-      if (!TRACK) put4(PMC, spm);
-      for (int lstep = 0; lstep < a.L; ++lstep) {           // S:427-461
-        const uint32_t k0 = 2u + 8u * (uint32_t)lstep;
-        if (TRACK) pair_tracked(WS, n, k0 + 1, k0 + 2, sth, sthc, spm, spmc, y, yc, z, zc);    // phi_A/2, phi_B/2  S:429-433
-        else {
-          half_step(n, k0 + 1, sth, PMC, sthc, spm, PM);    // phi_A/2  S:429-430
-          half_step(n, k0 + 2, sthc, PM, sth, spmc, PMC);   // phi_B/2  S:432-433
-        }
-        if (a.K == 0) __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {                       // phi_C    S:447-450, sequential (Q1)
-          T xx = sth[e], b = spm[e], xc = sthc[e], bc = spmc[e];
-          const T h = 0.5f, cc = a.rot_c, ss = a.rot_s;
-          xx = h * ((xx + xc) + cc * (xx - xc) + ss * (b - bc));
-          b = h * ((b + bc) - ss * (xx - xc) + cc * (b - bc));
-          xc = h * ((xx + xc) - cc * (xx - xc) - ss * (b - bc));
-          bc = h * ((b + bc) + ss * (xx - xc) - cc * (b - bc));
-          sth[e] = xx; spm[e] = b; sthc[e] = xc; spmc[e] = bc;
-        }
-        put4(PM, spm);
-        put4(PMC, spmc);
-        if (TRACK) {                                        // the four tracked products of the rotated state, afresh
-          T dt[4], dc[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { dt[e] = rok[e] ? sth[e] - mu_r[e] : 0.f; dc[e] = rok[e] ? sthc[e] - mu_r[e] : 0.f; }
-          put4(D1, dt);
-          put4(DC, dc);
-          __syncthreads();
-          bf4 p1 = {0.f, 0.f, 0.f, 0.f}, p2 = {0.f, 0.f, 0.f, 0.f}, s3 = {0.f, 0.f, 0.f, 0.f}, s4 = {0.f, 0.f, 0.f, 0.f};
-          prod4(D1, DC, PM, PMC, p1, p2, s3, s4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { y[e] = p1[e]; yc[e] = p2[e]; z[e] = s3[e]; zc[e] = s4[e]; }
-          pair_tracked(WS + 4 * MSZ, n, k0 + 4, k0 + 7, sthc, sth, spmc, spm, yc, y, zc, z);   // phi_B/2, phi_A/2  S:454-458
-        } else {
-          half_step(n, k0 + 4, sthc, PM, sth, spmc, PMC);   // phi_B/2  S:454-455
-          half_step(n, k0 + 7, sth, PMC, sthc, spm, PM);    // phi_A/2  S:457-458
-        }
-      }
-      if (TRACK) {                                          // (the tracked half steps keep the momenta in registers)
-        if (a.K == 0) __syncthreads();                      // no solve phase since the refresh phase read PM
-        put4(PM, spm);
-      }
-      T unused1[4], unused2[4];
-      hamiltonian(n, 2u + 8u * (uint32_t)a.L, sth, PM, spm, H1, lp1, unused1, unused2);   // S:989 (Q4)
-      // ---- Metropolis test + bookkeeping (S:1000-1026, S:1045-1057)
-      const T u = u23<T>(philox_block(a.seed, chain, n, PURPOSE_MH, 0, 0).x);
-      const bool acc = mh_accept<T>(H0, H1, lp1, u);
-      const bool reset = (!acc) && ((int)n == a.burn + 1);  // Q2
-      if (live) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (rok[e]) {
-            const T vnew = acc ? sth[e] : (reset ? a.theta_init[c * D + row0 + e] : scur[e]);
-            scur[e] = vnew;
-            if (a.samples && (int)n > a.burn) a.samples[((int64_t)((int)n - a.burn) * a.C + c) * D + row0 + e] = vnew;
-          }
-        }
-        if (w == 0 && blk == 0) {
-          if (a.H_old) a.H_old[(int64_t)t * a.C + c] = H0;
-          if (a.H_new) a.H_new[(int64_t)t * a.C + c] = H1;
-          if (a.accept) a.accept[(int64_t)t * a.C + c] = acc ? 1 : 0;
-        }
-      }
-      if (!acc) ++rejected;
-    }
-    if (live) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) if (rok[e]) a.cur[c * D + row0 + e] = scur[e];
-      if (w == 0 && blk == 0) a.reject_count[c] += rejected;
-    }
   }
-}
+};
 
-// =============================================================================================
-// The four-chain kernel on ALL FOUR SIMDs of a CU (the default from 513 to 1024 chains; "rmhmc_mfma4_waves" = 2 keeps the
-// two-wave kernel above, its parity reference).
-//
-// At 1024 chains there are 256 groups of four chains - one workgroup per CU - and the two-wave kernel leaves two of the four
-// matrix pipes of every CU idle.  Splitting the 128 (padded) rows over four waves alone would not help: the 16-block
-// instruction covers 64 rows at a time.  But its 16 blocks are INDEPENDENT 4 x 4 outer products, so here eight blocks take a
-// wave's 32 rows at the even contraction indices and the other eight the SAME rows at the odd ones: one instruction advances
-// k by two, a product is 50 (+2 padding) instructions per wave instead of 100, and the two partial sums of a row sit in lanes
-// l and l ^ 8 of one wave - combined by a DPP row rotation, no LDS, no barrier.  Per lane: 2 x 52 matrix operands instead of
-// 2 x 100.  The vectors live in LDS with even and odd rows apart (16-byte operand reads per parity).  Both parities run the
-// element-wise code (duplicate state, one writer), which frees a trick for the jitter: a half step's Philox block is the
-// most expensive scalar piece (quarter-rate integer multiplies), and the two parities draw the blocks of TWO half steps at
-// once and exchange them - two Philox passes per step instead of four.
-//
-// Round 2 added three things (measured steps: profiles/README.md, r02j-r02n):
-//  * TRACK ("rmhmc_pair" = 1, default): y = P (theta - mu), S p and their copies' twins are carried along element-wise, so a
-//    half step keeps only its K refinement products and the two half steps of a pair solve side by side (see the comment at
-//    `T y[4], ...` below): 5 product phases and 12 products per step at K = 2 instead of 8 and 16.
-//  * the operand fetch through the B-broadcast modifier of the instruction (blgp 4..7, see mfma_from_group): parity and chain
-//    of a lane depend only on its position inside its 16-lane group, so each group fetches a different 16-byte chunk and one
-//    LDS read feeds 16 instructions instead of 4.
-//  * the non-TRACK path ("rmhmc_pair" = 0) is the schedule of the two-wave kernel: same streams, same update order, same
-//    barriers; the sums run over even k then odd k (results agree to rounding).
-// =============================================================================================
-// (layout constants and the operand helpers: rmhmc_fused_dev.hpp)
-// LEAN ("rmhmc_lean"): see rmhmc_uv_kernel - no selects on the padding rows (TRACK paths): 2 897 -> 2 857 instructions per step.
-// (The stores keep their lane predicate here: without it the allocator of this 456-register kernel spills 22 values to scratch
-//  inside the step loop - tools/isa_of.py on the instance.)
-template <bool TRACK, bool LEAN = false>
-__global__ __launch_bounds__(XNT) void rmhmc_mfma4x4_kernel(FusedArgs<float> a) {
-  typedef float T;
+template <bool TRACK>
+__global__ __launch_bounds__(QNT) void rmhmc_mfma4_kernel(FusedArgs<float> a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* lds = reinterpret_cast<T*>(smem_raw);
-  constexpr int MSZ = XNC * XLD;
-  T* PM = lds; T* PMC = PM + MSZ; T* D0 = PMC + MSZ; T* D1 = D0 + MSZ; T* W0 = D1 + MSZ; T* W1 = W0 + MSZ; T* EV = W1 + MSZ;
-  T* DC = EV + MSZ;                                       // tracked products: theta_c - mu (D1: theta - mu)
-  T* WS = DC + MSZ;                                       // tracked products: 2 pairs x 2 solves x 2 refinement vectors
-  T* red = WS + 8 * MSZ;                                  // [XWV][XNC][4]
-  // lane bits: [1:0] chain, [2] low bit of the row block, [3] contraction parity, [5:4] 16-lane group = high bits of the row
-  // block.  The parity and the chain are functions of the lane's position INSIDE its 16-lane group, so a group's B operand
-  // serves all four groups (mfma_from_group): each group fetches a different 16-byte chunk of the vectors and one LDS read
-  // feeds 16 matrix instructions instead of 4 - with every lane fetching its own copy of every chunk the four waves' reads
-  // (1 KB per instruction) kept the LDS port busy 64 of every 67 clocks of matrix work.
-  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, cl = l & 3, grp = l >> 4;
-  const int kpar = (l >> 3) & 1, rb = 2 * grp + ((l >> 2) & 1);
-  const bool upper = kpar != 0, lead = (l >> 2) == 0;
-  const int D = a.D;
-  const int row0 = 32 * w + 4 * rb, arow = row0 + cl;     // this lane OWNS rows row0..row0+3 of chain cl and SUPPLIES matrix row arow
-  T Sa[XKJ], Pa[XKJ];
-#pragma unroll
-  for (int j = 0; j < XKJ; ++j) {
-    const int k = 2 * j + kpar;
-    const bool ok = arow < D && k < D;
-    Sa[j] = ok ? a.S[(int64_t)k * D + arow] : 0.f;        // symmetric: column arow, coalesced over the lanes
-    Pa[j] = ok ? a.P[(int64_t)k * D + arow] : 0.f;
-  }
-  T mu_r[4], sd_r[4];
-  bool rok[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int r = row0 + e;
-    rok[e] = r < D;
-    mu_r[e] = rok[e] ? a.mu[r] : 0.f;
-    sd_r[e] = rok[e] ? a.S[(int64_t)r * D + r] : 0.f;
-  }
-  for (int e = tid; e < XBUF * MSZ + XWV * XNC * 4; e += XNT) lds[e] = 0.f;
-  const T eh = 0.5f * a.eps;
-#if HTA_RM_TIMING
-  unsigned long long xacc[16] = {0}, xlast = 0;
-#endif
-  const int own_off = cl * XLD + (row0 >> 1);             // rows row0, row0+2 -> even half; row0+1, row0+3 -> odd half
-  const int b_off = cl * XLD + kpar * XHL + 4 * grp;      // this group's chunk of a super-chunk of four
-  int dpar = 0;
-  T ev_r[4] = {0.f, 0.f, 0.f, 0.f};
-  uint64_t chain = 0;
-  bool live = false;
-
-  typedef float bf2 __attribute__((ext_vector_type(2)));
-  auto put4 = [&](T* X, const T (&v)[4]) {
-    if (!upper) {
-      *reinterpret_cast<bf2*>(X + own_off) = bf2{v[0], v[2]};
-      *reinterpret_cast<bf2*>(X + own_off + XHL) = bf2{v[1], v[3]};
-    }
-  };
-  // the jitter of this lane's four rows for ONE sub-stream (uniform_elem layout: rows 4b..4b+3 are Philox block b)
-  auto jitter_raw = [&](uint32_t n, uint32_t sub, T (&out)[4]) {
-    const U4 r = philox_block(a.seed, chain, n, PURPOSE_JITTER, sub, (uint32_t)(row0 >> 2));
-    const T u[4] = {u23<T>(r.x), u23<T>(r.y), u23<T>(r.z), u23<T>(r.w)};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) out[e] = (live && rok[e]) ? a.jitter * u[e] : 0.f;
-  };
-  // two sub-streams with one Philox pass: the lower lane half draws subA, the upper half subB, then they swap
-  auto jitter_pair = [&](uint32_t n, uint32_t subA, uint32_t subB, T (&eA)[4], T (&eB)[4]) {
-    if (!a.has_jitter) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { eA[e] = 0.f; eB[e] = 0.f; }
-      return;
-    }
-    T mine[4];
-    jitter_raw(n, upper ? subB : subA, mine);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const T oth = other_parity(mine[e]);
-      eA[e] = upper ? oth : mine[e];
-      eB[e] = upper ? mine[e] : oth;
-    }
-  };
-  // super-chunk Q of a vector: 16 contraction indices of this lane's parity, 4 per 16-lane group
-  auto fetch = [&](const T* X, bf4 (&c)[XSQ]) {
-#pragma unroll
-    for (int Q = 0; Q < XSQ; ++Q) c[Q] = *reinterpret_cast<const bf4*>(X + b_off + 16 * Q);
-  };
-  auto both = [&](bf4& acc) {                                // lanes l and l ^ 8 both end with (even k) + (odd k)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] += other_parity(acc[e]);
-  };
-  // two products with one pass over k: acc1 = A1 X1, acc2 = A2 X2 (two independent accumulator chains); the four reads of
-  // each vector are issued up front (one wave per SIMD: nothing else hides an LDS round trip)
-  auto prod2 = [&](const T (&A1)[XKJ], const T* X1, const T (&A2)[XKJ], const T* X2, bf4& acc1, bf4& acc2) {
-    bf4 c1[XSQ], c2[XSQ];
-    fetch(X1, c1);
-    fetch(X2, c2);
-    __builtin_amdgcn_sched_barrier(0);                      // (the scheduler otherwise sinks the reads next to their use)
-    static_for(std::make_integer_sequence<int, XQ>{}, [&](auto qc) {
-      constexpr int q = decltype(qc)::value;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        acc1 = mfma_from_group<q % 4>(A1[4 * q + u], c1[q / 4][u], acc1);
-        acc2 = mfma_from_group<q % 4>(A2[4 * q + u], c2[q / 4][u], acc2);
-      }
-    });
-    both(acc1); both(acc2);
-  };
-  // one product on two accumulator chains (k in the order 0 2 | 1 3 of every chunk, as the two-wave kernel sums it)
-  auto prod1 = [&](const T (&A1)[XKJ], const T* X1, bool squared, bf4& acc) {
-    bf4 c1[XSQ], sb = {0.f, 0.f, 0.f, 0.f};
-    fetch(X1, c1);
-    __builtin_amdgcn_sched_barrier(0);
-    static_for(std::make_integer_sequence<int, XQ>{}, [&](auto qc) {
-      constexpr int q = decltype(qc)::value;
-#pragma unroll
-      for (int u = 0; u < 4; u += 2) {
-        const T a0 = A1[4 * q + u], a1 = A1[4 * q + u + 1];
-        acc = mfma_from_group<q % 4>(squared ? a0 * a0 : a0, c1[q / 4][u], acc);
-        sb = mfma_from_group<q % 4>(squared ? a1 * a1 : a1, c1[q / 4][u + 1], sb);
-      }
-    });
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] += sb[e];
-    both(acc);
-  };
-  // x = (P + diag(e))^-1 m continued from x0 = S m (rmhmc_fused_kernel: refine)
-  auto refine = [&](const T (&x0)[4], T (&xr)[4]) {
-    for (int it = 0; it < a.K; ++it) {
-      const T* wr = (it & 1) ? W1 : W0;
-      T* ww = (it & 1) ? W0 : W1;
-      __syncthreads();
-      bf4 sa = {0.f, 0.f, 0.f, 0.f};
-      prod1(Sa, wr, false, sa);
-      T wv[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { xr[e] = x0[e] - sa[e]; wv[e] = ev_r[e] * xr[e]; }
-      put4(ww, wv);
-    }
-  };
-  // one half step with the jitter in ev_r: upd_x += eh G(X)^-1 m ; upd_g -= eh P (X - mu)   (rmhmc_fused_kernel: half_step)
-  auto half_step = [&](const T (&X)[4], const T* m, T (&upd_x)[4], T (&upd_g)[4], T* upd_g_lds) {
-    T* d = dpar ? D1 : D0;
-    dpar ^= 1;
-    T dv[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) dv[e] = rok[e] ? X[e] - mu_r[e] : 0.f;
-    put4(d, dv);
-    __syncthreads();
-    bf4 Pd = {0.f, 0.f, 0.f, 0.f}, x0v = {0.f, 0.f, 0.f, 0.f};
-    prod2(Pa, d, Sa, m, Pd, x0v);
-    T x0[4], xr[4], wv[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      upd_g[e] -= eh * Pd[e];
-      x0[e] = x0v[e]; xr[e] = x0v[e];
-      wv[e] = ev_r[e] * x0v[e];
-    }
-    put4(upd_g_lds, upd_g);
-    put4(W0, wv);
-    refine(x0, xr);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) upd_x[e] += eh * xr[e];
-  };
-  // ---- TRACK: the half steps without their P d and S m products ------------------------------------------------------
-  // S = P^-1 is what makes this path possible in the first place, and it also makes two of a half step's K + 2 products
-  // redundant.  Keep y = P (theta - mu), y_c = P (theta_c - mu), z = S p, z_c = S p_c next to the four state vectors:
-  //   p -= eh P (theta - mu) = eh y           =>  z -= eh (theta - mu)                          (S P = I)
-  //   theta_c += eh x,  x = (P + E)^-1 p_c    =>  y_c += eh P x = eh (p_c - e . x_(K-1))         (x_K = S p_c - S (e . x_(K-1)))
-  // element-wise, exact for the iteration as implemented.  The solve starts from x_0 = S p_c = z_c: only its K refinement
-  // products remain, and the second half step of a pair (position theta_c, momentum the p just updated) no longer depends on
-  // the first one's solve: the two solves run side by side, one accumulator chain each - K product phases per PAIR of half
-  // steps instead of 2 (K + 1).  The rotation phi_C mixes all four vectors; right after it the four tracked products are
-  // evaluated afresh in one phase (so a tracked vector carries at most four element-wise updates of rounding).  Per step at
-  // K = 2: 5 barrier-separated phases and 12 products instead of 8 and 16.
-  T y[4], yc[4], z[4], zc[4];
-  auto prod4 = [&](const T* X1, const T* X2, const T* X3, const T* X4, bf4& p1, bf4& p2, bf4& s3, bf4& s4) {   // P X1, P X2, S X3, S X4
-    bf4 c1[XSQ], c2[XSQ], c3[XSQ], c4[XSQ];
-    fetch(X1, c1); fetch(X2, c2); fetch(X3, c3); fetch(X4, c4);
-    __builtin_amdgcn_sched_barrier(0);
-    static_for(std::make_integer_sequence<int, XQ>{}, [&](auto qc) {
-      constexpr int q = decltype(qc)::value;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        p1 = mfma_from_group<q % 4>(Pa[4 * q + u], c1[q / 4][u], p1);
-        p2 = mfma_from_group<q % 4>(Pa[4 * q + u], c2[q / 4][u], p2);
-        s3 = mfma_from_group<q % 4>(Sa[4 * q + u], c3[q / 4][u], s3);
-        s4 = mfma_from_group<q % 4>(Sa[4 * q + u], c4[q / 4][u], s4);
-      }
-    });
-    both(p1); both(p2); both(s3); both(s4);
-  };
-  // two independent solves x = (P + E)^-1 m from x_0 = S m, K phases; wa / wb return e . x_(K-1) (zero without jitter)
-  auto solve2 = [&](T* WB, const T (&ea)[4], const T (&eb)[4], const T (&x0a)[4], const T (&x0b)[4], T (&xa)[4], T (&xb)[4],
-                    T (&wa)[4], T (&wb)[4]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { xa[e] = x0a[e]; xb[e] = x0b[e]; wa[e] = 0.f; wb[e] = 0.f; }
-    for (int it = 0; it < a.K; ++it) {
-      T* A = WB + (it & 1) * MSZ;                           // read in this phase only; rewritten two phases later
-      T* B = A + 2 * MSZ;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { wa[e] = ea[e] * xa[e]; wb[e] = eb[e] * xb[e]; }
-      put4(A, wa);
-      put4(B, wb);
-      HTA_XTICK(3);
-      __syncthreads();
-      HTA_XTICK(1);
-      bf4 ra = {0.f, 0.f, 0.f, 0.f}, rb = {0.f, 0.f, 0.f, 0.f};
-      prod2(Sa, A, Sa, B, ra, rb);
-      HTA_XTICK(2);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { xa[e] = x0a[e] - ra[e]; xb[e] = x0b[e] - rb[e]; }
-    }
-  };
-  // a pair of half steps (S:429-433 and, with the roles of the copies swapped, S:454-458):
-  //   a:  g1 -= eh P (X1 - mu)   X2 += eh (P + E_a)^-1 g2        b:  g2 -= eh P (X2 - mu)   X1 += eh (P + E_b)^-1 g1
-  // with y1 = P (X1 - mu), y2 = P (X2 - mu), z1 = S g1, z2 = S g2 kept current
-  auto pair_tracked = [&](T* WB, const T (&ea)[4], const T (&eb)[4], T (&X1)[4], T (&X2)[4], T (&g1)[4], T (&g2)[4],
-                          T (&y1)[4], T (&y2)[4], T (&z1)[4], T (&z2)[4]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      g1[e] -= eh * y1[e];                                  // a's momentum update ...
-      z1[e] -= eh * ((LEAN || rok[e]) ? X1[e] - mu_r[e] : 0.f);       // ... and S g1 with it
-    }
-    T xa[4], xb[4], wa[4], wb[4];
-    solve2(WB, ea, eb, z2, z1, xa, xb, wa, wb);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      X2[e] += eh * xa[e];                                  // a's position update; P x_a = g2 - e_a . x_a(K-1)
-      y2[e] += eh * (g2[e] - wa[e]);
-      g2[e] -= eh * y2[e];                                  // b's momentum update
-      z2[e] -= eh * ((LEAN || rok[e]) ? X2[e] - mu_r[e] : 0.f);
-      X1[e] += eh * xb[e];                                  // b's position update
-      y1[e] += eh * (g1[e] - wb[e]);
-    }
-    HTA_XTICK(3);
-  };
-  // three sums per chain over the rows, complete in every lane of the chain's column (the upper lane half holds duplicates
-  // of the lower one: it contributes nothing)
-  auto block_sums = [&](T (&v)[3]) {
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-      if (upper) v[e] = 0.f;
-      v[e] += __shfl_xor(v[e], 4, 64);
-      v[e] += __shfl_xor(v[e], 16, 64);
-      v[e] += __shfl_xor(v[e], 32, 64);
-    }
-    __syncthreads();
-    if (lead) {
-#pragma unroll
-      for (int e = 0; e < 3; ++e) red[(w * XNC + cl) * 4 + e] = v[e];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-      T s = 0.f;
-#pragma unroll
-      for (int i = 0; i < XWV; ++i) s += red[(i * XNC + cl) * 4 + e];
-      v[e] = s;
-    }
-  };
-  // H = -log p + D/2 log 2 pi + 1/2 log|G| + 1/2 m^T G^-1 m  (S:731)   (rmhmc_fused_kernel: hamiltonian, series branch)
-  auto hamiltonian = [&](uint32_t n, uint32_t sub, const T (&X)[4], const T* m, const T (&mr)[4], T& H, T& logp, T (&Pd_out)[4],
-                         T (&Sm_out)[4]) {
-    T* d = (dpar && !TRACK) ? D1 : D0;                      // (TRACK: D1 belongs to the refresh phase)
-    dpar ^= 1;
-    if (a.has_jitter) jitter_raw(n, sub, ev_r);
-    T dr[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) dr[e] = rok[e] ? X[e] - mu_r[e] : 0.f;
-    put4(EV, ev_r);
-    put4(d, dr);
-    __syncthreads();
-    bf4 Pd = {0.f, 0.f, 0.f, 0.f}, x0v = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-    prod2(Pa, d, Sa, m, Pd, x0v);
-    if (a.has_jitter) prod1(Sa, EV, true, s2);              // second-order log-det term: (S . S) e
-    T v[3] = {0.f, 0.f, 0.f}, x0[4], xr[4], wv[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      x0[e] = x0v[e]; xr[e] = x0v[e];
-      Pd_out[e] = Pd[e]; Sm_out[e] = x0v[e];
-      v[0] += dr[e] * Pd[e];
-      wv[e] = ev_r[e] * x0v[e];
-      if (a.has_jitter) v[2] += ev_r[e] * (sd_r[e] - 0.5f * s2[e]);      // log|P + E| = log|P| + tr(SE) - 1/2 tr((SE)^2) + ...
-    }
-    put4(W0, wv);
-    refine(x0, xr);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[1] += mr[e] * xr[e];
-    block_sums(v);
-    const float pi_term = (float)D * 1.8378770351409912f;   // S:712
-    logp = a.log_norm - 0.5f * v[0];
-    H = -logp + 0.5f * pi_term + 0.5f * (a.logdetP + v[2]) + 0.5f * v[1];
-  };
-
-  const int64_t ngroup = (a.C + XNC - 1) / XNC;
-  for (int64_t cg = blockIdx.x; cg < ngroup; cg += gridDim.x) {
-    const int64_t c = XNC * cg + cl;
-    live = c < a.C;
-    chain = a.chain_offset + (uint64_t)(live ? c : 0);
-    T scur[4], sth[4], spm[4], sthc[4], spmc[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) scur[e] = (live && rok[e]) ? a.cur[c * D + row0 + e] : 0.f;
-    int32_t rejected = 0;
-    // this lane's four rows of the pre-drawn momentum of local trajectory tt as four UNCONDITIONAL loads (a lane without a row
-    // reads element 0 of the block and discards it; offsets masked with masks the optimiser cannot trace back to `live` - a
-    // select comes back as a branch around each load with its own s_waitcnt vmcnt(0)): issued back to back, and for trajectory
-    // t + 1 a whole trajectory before their use (momentum_use pins the first use of the loaded registers where it stands)
-    int lmask = -(int)live, rmask[4];
-    asm volatile("" : "+v"(lmask));
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { rmask[e] = -(int)rok[e]; asm volatile("" : "+v"(rmask[e])); }
-    auto momentum_raw = [&](int tt, T (&v)[4]) {
-      const T* prow = a.p_ws + ((int64_t)tt * a.C + (int64_t)((int)c & lmask)) * D;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = prow[(row0 + e) & rmask[e] & lmask];
-    };
-    auto momentum_use = [&](T (&v)[4], T (&out)[4]) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { asm volatile("" : "+v"(v[e])); out[e] = (live && rok[e]) ? v[e] : 0.f; }
-    };
-    T pnext[4];
-    if (a.n_traj > 0) momentum_raw(0, pnext);
-    __syncthreads();                                        // the previous group's last reads of the vector matrices
-#if HTA_RM_TIMING
-    xlast = __builtin_readcyclecounter();
-#endif
-    for (int t = 0; t < a.n_traj; ++t) {
-      const uint32_t n = (uint32_t)(a.traj_offset + t);
-      // ---- gibbs: p = chol(G(theta)) z, drawn ahead by the momentum kernel (S:183-184)
-      momentum_use(pnext, spm);
-      if (t + 1 < a.n_traj) momentum_raw(t + 1, pnext);
-      put4(PM, spm);
-      HTA_XTICK(7);
-      T H0, H1, lp0, lp1;
-      hamiltonian(n, 1, scur, PM, spm, H0, lp0, y, z);      // S:971 -> S:822
-      HTA_XTICK(5);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { sth[e] = scur[e]; sthc[e] = scur[e]; spmc[e] = spm[e]; yc[e] = y[e]; zc[e] = z[e]; }   // S:425-426
-      if (!TRACK) put4(PMC, spm);
-      for (int lstep = 0; lstep < a.L; ++lstep) {           // S:427-461
-        const uint32_t k0 = 2u + 8u * (uint32_t)lstep;
-        T e1[4], e2[4];
-        jitter_pair(n, k0 + 1, k0 + 2, e1, e2);
-        HTA_XTICK(0);
-        if (TRACK) pair_tracked(WS, e1, e2, sth, sthc, spm, spmc, y, yc, z, zc);     // phi_A/2, phi_B/2  S:429-433
-        else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ev_r[e] = e1[e];
-          half_step(sth, PMC, sthc, spm, PM);               // phi_A/2  S:429-430
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ev_r[e] = e2[e];
-          half_step(sthc, PM, sth, spmc, PMC);              // phi_B/2  S:432-433
-        }
-        if (a.K == 0) __syncthreads();
-        jitter_pair(n, k0 + 4, k0 + 7, e1, e2);             // (issued before the rotation: independent work for the scheduler)
-        HTA_XTICK(0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {                       // phi_C    S:447-450, sequential (Q1)
-          T xx = sth[e], b = spm[e], xc = sthc[e], bc = spmc[e];
-          const T h = 0.5f, cc = a.rot_c, ss = a.rot_s;
-          xx = h * ((xx + xc) + cc * (xx - xc) + ss * (b - bc));
-          b = h * ((b + bc) - ss * (xx - xc) + cc * (b - bc));
-          xc = h * ((xx + xc) - cc * (xx - xc) - ss * (b - bc));
-          bc = h * ((b + bc) + ss * (xx - xc) - cc * (b - bc));
-          sth[e] = xx; spm[e] = b; sthc[e] = xc; spmc[e] = bc;
-        }
-        put4(PM, spm);
-        put4(PMC, spmc);
-        if (TRACK) {                                        // the four tracked products of the rotated state, afresh
-          T dt[4], dc[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { dt[e] = (LEAN || rok[e]) ? sth[e] - mu_r[e] : 0.f; dc[e] = (LEAN || rok[e]) ? sthc[e] - mu_r[e] : 0.f; }
-          put4(D1, dt);
-          put4(DC, dc);
-          HTA_XTICK(4);
-          __syncthreads();
-          HTA_XTICK(1);
-          bf4 p1 = {0.f, 0.f, 0.f, 0.f}, p2 = {0.f, 0.f, 0.f, 0.f}, s3 = {0.f, 0.f, 0.f, 0.f}, s4 = {0.f, 0.f, 0.f, 0.f};
-          prod4(D1, DC, PM, PMC, p1, p2, s3, s4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { y[e] = p1[e]; yc[e] = p2[e]; z[e] = s3[e]; zc[e] = s4[e]; }
-          HTA_XTICK(2);
-          pair_tracked(WS + 4 * MSZ, e1, e2, sthc, sth, spmc, spm, yc, y, zc, z);    // phi_B/2, phi_A/2  S:454-458
-        } else {
-          HTA_XTICK(4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ev_r[e] = e1[e];
-          half_step(sthc, PM, sth, spmc, PMC);              // phi_B/2  S:454-455
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ev_r[e] = e2[e];
-          half_step(sth, PMC, sthc, spm, PM);               // phi_A/2  S:457-458
-        }
-      }
-      if (TRACK) {                                          // (the tracked half steps keep the momenta in registers)
-        if (a.K == 0) __syncthreads();                      // no solve phase since the refresh phase read PM
-        put4(PM, spm);
-      }
-      T unused1[4], unused2[4];
-      hamiltonian(n, 2u + 8u * (uint32_t)a.L, sth, PM, spm, H1, lp1, unused1, unused2);   // S:989 (Q4)
-      HTA_XTICK(5);
-      // ---- Metropolis test + bookkeeping (S:1000-1026, S:1045-1057)
-      const T u = u23<T>(philox_block(a.seed, chain, n, PURPOSE_MH, 0, 0).x);
-      const bool acc = mh_accept<T>(H0, H1, lp1, u);
-      const bool reset = (!acc) && ((int)n == a.burn + 1);  // Q2
-      if (live) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (rok[e]) {
-            const T vnew = acc ? sth[e] : (reset ? a.theta_init[c * D + row0 + e] : scur[e]);
-            scur[e] = vnew;
-            if (!upper && a.samples && (int)n > a.burn) a.samples[((int64_t)((int)n - a.burn) * a.C + c) * D + row0 + e] = vnew;
-          }
-        }
-        if (w == 0 && lead) {
-          if (a.H_old) a.H_old[(int64_t)t * a.C + c] = H0;
-          if (a.H_new) a.H_new[(int64_t)t * a.C + c] = H1;
-          if (a.accept) a.accept[(int64_t)t * a.C + c] = acc ? 1 : 0;
-        }
-      }
-      if (!acc) ++rejected;
-      HTA_XTICK(6);
-    }
-    if (live) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) if (rok[e] && !upper) a.cur[c * D + row0 + e] = scur[e];
-      if (w == 0 && lead) a.reject_count[c] += rejected;
-    }
-  }
-#if HTA_RM_TIMING
-  if (tid == 0 && blockIdx.x == 0) for (int k = 0; k < 16; ++k) hta_rm_dbg[k] = xacc[k];
-#endif
+  Mfma4Tile t(a, reinterpret_cast<float*>(smem_raw));
+  rows4_trajectories<TRACK>(a, t);
 }
 
 // The momentum draws of a block of trajectories, off the chains' critical path: task (t, c) -> p = chol(P + diag(e)) z
@@ -2466,23 +1555,10 @@ int rmhmc_fused_sample(T* cur, const T* theta_init, const T* P, const T* Sinv, c
         if (quad4) {
           const int64_t ngroup = (C + QNC - 1) / QNC;
           profile_begin(s);
-          // four waves per group while the groups fit one per CU (<= 1024 chains on 256 CUs): beyond that two groups share a CU
-          // and the two-wave kernel already fills its four SIMDs
-          const bool two_wave = g_rmhmc_mfma4_waves == 2 || (g_rmhmc_mfma4_waves != 5 && ngroup > 256);
-          note_route("%s<%s>", two_wave ? "rmhmc_mfma4_kernel" : "rmhmc_mfma4x4_kernel", g_rmhmc_pair ? "true" : "false");
-          if (two_wave) {
-            const size_t qlds = (size_t)(QBUF * QNC * QLD + QWV * QNC * 4) * sizeof(float);
-            if (g_rmhmc_pair) rmhmc_mfma4_kernel<true><<<(int)(ngroup < 8192 ? ngroup : 8192), QNT, qlds, s>>>(a);
-            else rmhmc_mfma4_kernel<false><<<(int)(ngroup < 8192 ? ngroup : 8192), QNT, qlds, s>>>(a);
-          } else {
-            const size_t xlds = (size_t)(XBUF * XNC * XLD + XWV * XNC * 4) * sizeof(float);
-            if (g_rmhmc_pair && g_rmhmc_lean) {
-              note_route("rmhmc_mfma4x4_kernel<true,lean>");
-              rmhmc_mfma4x4_kernel<true, true><<<(int)(ngroup < 8192 ? ngroup : 8192), XNT, xlds, s>>>(a);
-            }
-            else if (g_rmhmc_pair) rmhmc_mfma4x4_kernel<true><<<(int)(ngroup < 8192 ? ngroup : 8192), XNT, xlds, s>>>(a);
-            else rmhmc_mfma4x4_kernel<false><<<(int)(ngroup < 8192 ? ngroup : 8192), XNT, xlds, s>>>(a);
-          }
+          note_route("rmhmc_mfma4_kernel<%s>", g_rmhmc_pair ? "true" : "false");
+          const size_t qlds = (size_t)(QBUF * QNC * QLD + QWV * QNC * 4) * sizeof(float);
+          if (g_rmhmc_pair) rmhmc_mfma4_kernel<true><<<(int)(ngroup < 8192 ? ngroup : 8192), QNT, qlds, s>>>(a);
+          else rmhmc_mfma4_kernel<false><<<(int)(ngroup < 8192 ? ngroup : 8192), QNT, qlds, s>>>(a);
           profile_end(s);
           return HTA_OK;
         }

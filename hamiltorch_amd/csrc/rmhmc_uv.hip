@@ -2,7 +2,7 @@
 // it computes: hamiltorch/samplers.py:969-1026 with the integrator S:425-461), ONE or TWO chains per workgroup on the matrix
 // cores: the kernel for BASELINE config 3 (256 chains) and for every chain count up to 2 x (compute units).
 //
-// The tracked schedule of rmhmc_mfma4x4_kernel (a half step keeps only its K refinement products; the two half steps of a pair
+// The tracked schedule derived in rows4_trajectories, rmhmc_rows4_dev.hpp (a half step keeps only its K refinement products; the two half steps of a pair
 // solve side by side) has, per chain, exactly two vectors in flight in every product phase: one of the state set
 // U = (theta, p, y = P (theta - mu), z = S p) and one of the copy V = (theta_c, p_c, y_c, z_c).  Here those two vectors are two
 // COLUMNS of the 16-block instruction v_mfma_f32_4x4x1_16b_f32 (N = 4: chain 0's U and V, chain 1's U and V), so a phase is ONE
@@ -13,8 +13,8 @@
 // with x = (P + E)^-1 g from x_0 = z and w = e . x_(K-1).  The rotation phi_C (S:447-450) needs both sets in one lane: the
 // columns exchange their X and g through a DPP quad permutation, both compute the (sequential, Q1) rotation and keep their half;
 // right after it y and z are evaluated afresh (P (X - mu) and S g: one phase, two accumulator chains).  Rows x contraction
-// parity inside a wave, operand fetch through the B-broadcast modifier, LDS layout: as rmhmc_mfma4x4_kernel
-// (rmhmc_fused_dev.hpp).  Per step at K = 2: 5 phases, 312 matrix instructions per wave (the one-chain VALU kernel: 8 phases,
+// parity inside a wave, operand fetch through the B-broadcast modifier, LDS layout: rmhmc_fused_dev.hpp.
+//  Per step at K = 2: 5 phases, 312 matrix instructions per wave (the one-chain VALU kernel: 8 phases,
 // 896 v_fmac_f32_dpp per lane at about 9 clocks each).  Same Philox streams, same update order, same bookkeeping (Q1, Q2, Q4).
 #include <math.h>
 #include "rmhmc_fused_dev.hpp"
@@ -31,7 +31,7 @@ namespace hta {
 constexpr int UBUF = 9;            // LDS vector matrices: DV GV EV W0 W1 + 4 solve buffers [pair][iteration parity]
 
 // LEAN (tuning key "rmhmc_lean", default 1; measured: profiles/r03y_ab_lines.txt - 256 chains 8.12e7 -> 8.25e7, 1024 chains
-// (rmhmc_mfma4x4_kernel) 1.847e8 -> 1.870e8 explicit steps/s): the same arithmetic with fewer instructions around it - these kernels run one
+// (the four-wave four-chain kernel, since removed) 1.847e8 -> 1.870e8 explicit steps/s): the same arithmetic with fewer instructions around it - these kernels run one
 // wave per SIMD: nothing hides an instruction of the element-wise / bookkeeping stretches between their matrix phases
 // ("what comes next").  (i) put4 without its lane predicate: the upper lane half holds bit-identical duplicates of
 // the lower one's values ("duplicate state, one writer"), so both halves store - same address, same value - and the

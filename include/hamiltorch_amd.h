@@ -507,7 +507,7 @@ int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int it
  * p = chol(P) z1 + sqrt(jitter u) . z2 - covariance P + diag(jitter u) = G exactly, the law of S:183-184, chol(P) once per target;
  * 0 = chol(G) z with a factorisation per draw, the reference's arithmetic), "rmhmc_batch" (1 default: 16 chains per workgroup on the matrix cores from 2048 chains on; 0 off, 2 always),
  * "rmhmc_mfma4" (1 default: 4 chains per workgroup on v_mfma_f32_4x4x1_16b for "rmhmc_mfma4_lo" = 1793 (round 4; before: 513) <= chains < "rmhmc_mfma4_hi" = 2049;
- * 0 off, 2 always; "rmhmc_mfma4_waves" 4 default: four waves per group - rows x contraction parity inside a wave; 2 = two waves;
+ * 0 off, 2 always: rmhmc_mfma4_kernel, two waves per group of four chains;
  * "netn_waves" 1 default: waves per chain of the small-network kernel (2 / 4: a chain's sweeps over several waves where they fit);
  * "rmhmc_uv" 1 default: up to 7 x (compute units) chains (2 x with "rmhmc_uv_co" = 0) run one or two per workgroup with their state sets as columns of the
  * matrix instruction - csrc/rmhmc_uv.hip; 0 off, 2 at any chain count;
@@ -549,8 +549,8 @@ int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int it
  * 0 = the round-1 instance.  Bit-identical results; 78.5 / 74.1 / 73.25 instructions per trajectory of a lone wave at L = 25:
  * 166.3 -> 157.5 us per 1000 trajectories of BASELINE config 2),
  * "rmhmc_lean" (1 default: rmhmc_uv_kernel without the lane predicate around its LDS stores - both lane halves hold the same
- * values - and, with rmhmc_mfma4x4_kernel, without the selects that zero the padding rows, which are exact zeros by
- * construction: the same results bit for bit, ~30 instructions fewer per step of these one-wave-per-SIMD kernels (+1.6 % / +1.2 %);
+ * values - and without the selects that zero the padding rows, which are exact zeros by
+ * construction: the same results bit for bit, ~30 instructions fewer per step of this one-wave-per-SIMD kernel (+1.6 %);
  * 0 = the round-2 instances, the parity partners),
  * "rmhmc_uv_co" (round 4; 1 default = rmhmc_uv_kernel / rmhmc_uvc*_kernel under a 256-register cap, two workgroups per CU: the phase latency of one is
  * filled by the other's matrix instructions; bit-identical to 0; also extends the kernel's range to 4 x CUs chains),
@@ -587,7 +587,7 @@ int hta_set_tuning(const char* key, int value);
 int hta_get_tuning(const char* key, int* value);
 int hta_reset_tuning(void);
 /* Name (with template arguments) of the dominant kernel the calling thread's last sampling / evaluation call dispatched
- * to, e.g. "hmc_gauss_quad_kernel<3,false,25>", "rmhmc_uv_kernel<1>", "rmhmc_mfma4x4_kernel<true>", "mlp_mfma_kernel<2,7,0,512>".
+ * to, e.g. "hmc_gauss_quad_kernel<3,false,25>", "rmhmc_uv_kernel<1>", "rmhmc_mfma4_kernel<true>", "mlp_mfma_kernel<2,7,0,512>".
  * The string lives in thread-local storage until the next call.  Parity tests and bench.py assert / report the route
  * they exercise with it (the dispatch depends on the chain count and on the process-global tuning keys). */
 const char* hta_last_route(void);

@@ -662,14 +662,18 @@ def test_fused_momentum_overlap_equals_serial(ht, T, split):
 def test_batched_mfma_kernel_equals_fused_kernel(ht, D, C, jit):
     """rmhmc_batch_kernel (16 chains per workgroup, S X and P X as v_mfma_f32_16x16x4_f32 tiles) against rmhmc_fused_kernel
     (one chain per workgroup, the parity reference of this path): same streams and update order, sums in a different order ->
-    chain by chain to rounding, with ragged groups, burn-in (Q2 reset) and without jitter."""
+    chain by chain to rounding, with ragged groups, burn-in (Q2 reset) and without jitter.  On one shape of each BKJ instance
+    also "rmhmc_pair" = 0 (every product of every half step instead of the tracked products).  The route of every launch is
+    asserted: a silent fall-back would compare the reference with itself."""
     from hamiltorch_amd import _abi
     T, L, burn = 9, 3, 2
     t, _ = cfg3_target(ht, D, torch.float32, seed=9)
     th0 = tt((0.3 * O.philox_normals(3, np.arange(C), 0, D, O.PURPOSE_INIT, dtype=np.float64)).astype(np.float32), torch.float32)
     outs = []
-    for mode in (2, 0):
+    modes = [(2, 1), (0, 1)] + ([(2, 0)] if (D, C) in ((24, 40), (112, 17)) else [])
+    for mode, pair in modes:
         _abi.set_tuning("rmhmc_batch", mode)
+        _abi.set_tuning("rmhmc_pair", pair)         # 1: tracked products (default), 0: every product of every half step
         _abi.set_tuning("rmhmc_mfma4", 0)           # (from 513 to 2048 chains the default route is a four-chain kernel,
         _abi.set_tuning("rmhmc_uv", 0)              #  up to 512 chains rmhmc_uv_kernel)
         try:
@@ -678,18 +682,23 @@ def test_batched_mfma_kernel_equals_fused_kernel(ht, D, C, jit):
             ws = torch.empty(_abi.rmhmc_workspace_bytes(C, D, 4, T), dtype=torch.uint8, device=dev())
             _abi.rmhmc_gaussian_sample(cur, th0, t.precision, t.mean, t.log_norm, _abi.METRIC_SOFTABS, 1e6, jit, L, 0.1, 10.0,
                                        T, 0, burn, 21, 0, samples, rej, ws)
+            route = _abi.last_route()
             torch.cuda.synchronize()
         finally:
             _abi.set_tuning("rmhmc_batch", 1)
+            _abi.set_tuning("rmhmc_pair", 1)
             _abi.set_tuning("rmhmc_mfma4", 1)
             _abi.set_tuning("rmhmc_uv", 1)
+        want = "rmhmc_batch_kernel<%d,%s>" % (25 if D <= 100 else 28, "true" if pair else "false") if mode else "rmhmc_fused_kernel"
+        assert route.startswith(want), (route, want)
         outs.append((samples.cpu().numpy(), rej.cpu().numpy(), cur.cpu().numpy()))
-    err = np.abs(outs[0][0] - outs[1][0]).max(axis=(0, 2))
-    assert (err > 2e-4).mean() <= 0.05, "max err %.3g (%d chains differ)" % (err.max(), (err > 2e-4).sum())
-    good = err <= 2e-4
-    assert np.array_equal(outs[0][1][good], outs[1][1][good])
-    np.testing.assert_allclose(outs[0][2][good], outs[1][2][good], atol=2e-4)
-    assert np.abs(outs[0][0][T - 1 - burn] - outs[0][0][1]).max() > 1e-3          # rows 1 .. T-1-burn are written
+    for out in [outs[0]] + outs[2:]:                                               # pair 1, then pair 0, against the one-chain kernel
+        err = np.abs(out[0] - outs[1][0]).max(axis=(0, 2))
+        assert (err > 2e-4).mean() <= 0.05, "max err %.3g (%d chains differ)" % (err.max(), (err > 2e-4).sum())
+        good = err <= 2e-4
+        assert np.array_equal(out[1][good], outs[1][1][good])
+        np.testing.assert_allclose(out[2][good], outs[1][2][good], atol=2e-4)
+        assert np.abs(out[0][T - 1 - burn] - out[0][1]).max() > 1e-3              # rows 1 .. T-1-burn are written
 
 
 @pytest.mark.parametrize("D,C,jit,batch", [(7, 19, 1e-3, 0), (24, 40, 1e-2, 0), (50, 33, 1e-3, 0), (77, 21, 1e-3, 0),
@@ -809,17 +818,17 @@ def test_tracked_products_equal_explicit_products(ht, D, C, jit):
 def test_mfma4_kernel_equals_fused_kernel(ht, D, C, jit):
     """rmhmc_mfma4_kernel (4 chains per two-wave workgroup, S X and P X on v_mfma_f32_4x4x1_16b_f32) against rmhmc_fused_kernel
     (one chain per workgroup): same streams and update order, sums in a different order -> chain by chain to rounding, with
-    ragged groups, burn-in (Q2 reset), D on both sides of a wave's 64 rows, and without jitter."""
+    ragged groups, burn-in (Q2 reset), D on both sides of a wave's 64 rows, and without jitter; and the tracked products
+    ("rmhmc_pair" = 1) against every product of every half step (0).  The route of every launch is asserted: a silent
+    fall-back would compare the reference with itself."""
     from hamiltorch_amd import _abi
     T, L, burn = 9, 3, 2
     t, _ = cfg3_target(ht, D, torch.float32, seed=9)
     th0 = tt((0.3 * O.philox_normals(3, np.arange(C), 0, D, O.PURPOSE_INIT, dtype=np.float64)).astype(np.float32), torch.float32)
     outs = []
     try:
-        on = 2 if C < 513 else 1                                 # from 513 to 2048 chains it is the default route
-        for mode, waves, pair in ((on, 4, 1), (0, 4, 1), (on, 2, 1), (on, 4, 0)):
+        for mode, pair in ((2, 1), (0, 1), (2, 0)):              # (by default the route of 1793 .. 2048 chains only)
             _abi.set_tuning("rmhmc_mfma4", mode)
-            _abi.set_tuning("rmhmc_mfma4_waves", waves)          # 4: rmhmc_mfma4x4_kernel (default), 2: rmhmc_mfma4_kernel
             _abi.set_tuning("rmhmc_pair", pair)                  # 1: tracked products (default), 0: every product of every half step
             _abi.set_tuning("rmhmc_batch", 0)
             _abi.set_tuning("rmhmc_uv", 0)                       # (mode 0: the one-chain kernel, the reference)
@@ -828,18 +837,18 @@ def test_mfma4_kernel_equals_fused_kernel(ht, D, C, jit):
             ws = torch.empty(_abi.rmhmc_workspace_bytes(C, D, 4, T), dtype=torch.uint8, device=dev())
             _abi.rmhmc_gaussian_sample(cur, th0, t.precision, t.mean, t.log_norm, _abi.METRIC_SOFTABS, 1e6, jit, L, 0.1, 10.0,
                                        T, 0, burn, 21, 0, samples, rej, ws)
+            route = _abi.last_route()
             torch.cuda.synchronize()
+            want = "rmhmc_mfma4_kernel<%s" % ("true" if pair else "false") if mode else "rmhmc_fused_kernel"
+            assert route.startswith(want), (route, want)
             outs.append((samples.cpu().numpy(), rej.cpu().numpy(), cur.cpu().numpy()))
     finally:
         _abi.set_tuning("rmhmc_mfma4", MFMA4_DEFAULT)
-        _abi.set_tuning("rmhmc_mfma4_waves", 4)
         _abi.set_tuning("rmhmc_pair", 1)
         _abi.set_tuning("rmhmc_batch", 1)
         _abi.set_tuning("rmhmc_uv", 1)
     assert np.isfinite(outs[0][0]).all()
-    err2 = np.abs(outs[0][0] - outs[2][0]).max(axis=(0, 2))          # four-wave kernel against the two-wave kernel
-    assert (err2 > 2e-4).mean() <= 0.05, "four- vs two-wave kernel: max err %.3g (%d chains differ)" % (err2.max(), (err2 > 2e-4).sum())
-    err3 = np.abs(outs[0][0] - outs[3][0]).max(axis=(0, 2))          # paired half steps against one half step at a time
+    err3 = np.abs(outs[0][0] - outs[2][0]).max(axis=(0, 2))          # paired half steps against one half step at a time
     assert (err3 > 2e-4).mean() <= 0.05, "paired vs single half steps: max err %.3g (%d chains differ)" % (err3.max(), (err3 > 2e-4).sum())
     err = np.abs(outs[0][0] - outs[1][0]).max(axis=(0, 2))
     assert (err > 2e-4).mean() <= 0.05, "max err %.3g (%d chains differ)" % (err.max(), (err > 2e-4).sum())
@@ -1323,13 +1332,13 @@ def test_metric_general_mode_restarts_the_basis_of_a_system_that_went_non_finite
     np.testing.assert_allclose(x.cpu().numpy(), want, rtol=2e-3, atol=2e-3)
 
 
-@pytest.mark.parametrize("C,D,route", [(256, 100, "rmhmc_uv_kernel<1"), (512, 100, "rmhmc_uv_kernel<2"), (1024, 100, "rmhmc_mfma4x4_kernel<true"),
-                                       (300, 37, "rmhmc_uv_kernel<2"), (700, 90, "rmhmc_mfma4x4_kernel<true")])
+@pytest.mark.parametrize("C,D,route", [(256, 100, "rmhmc_uv_kernel<1"), (512, 100, "rmhmc_uv_kernel<2"),
+                                       (300, 37, "rmhmc_uv_kernel<2")])
 def test_lean_instances_of_the_lone_wave_kernels_are_bit_identical(ht, C, D, route):
     """hta_set_tuning('rmhmc_lean', 1): rmhmc_uv_kernel without the lane predicate around its LDS stores (both lane halves
-    hold the same values) and, with rmhmc_mfma4x4_kernel, without the selects that zero the padding rows (exact zeros by
+    hold the same values) and without the selects that zero the padding rows (exact zeros by
     construction) - fewer instructions per step of kernels whose time is their instruction count.  Same samples, reject
-    counts and final state bit for bit, with jitter, with a mean offset, with padding rows (D = 37, 90, 100 < 128) and with a
+    counts and final state bit for bit, with jitter, with a mean offset, with padding rows (D = 37, 100 < 128) and with a
     chain that diverges (it is rejected and must sample on, exactly as in the default instance)."""
     from hamiltorch_amd import _abi
     t, _ = cfg3_target(ht, D, torch.float32, seed=D)
@@ -1340,7 +1349,7 @@ def test_lean_instances_of_the_lone_wave_kernels_are_bit_identical(ht, C, D, rou
     outs = []
     for lean in (0, 1):
         _abi.set_tuning("rmhmc_lean", lean)
-        _abi.set_tuning("rmhmc_uvc", 0); _abi.set_tuning("rmhmc_uv_co", 0); _abi.set_tuning("rmhmc_mfma4_lo", 513)   # the round-3 routes
+        _abi.set_tuning("rmhmc_uvc", 0); _abi.set_tuning("rmhmc_uv_co", 0)   # the round-3 routes
         try:
             cur = th0.clone(); samples = torch.zeros(T + 1, C, D, device=dev()); rej = torch.zeros(C, dtype=torch.int32, device=dev())
             ws = torch.zeros(_abi.rmhmc_workspace_bytes(C, D, 4, T), dtype=torch.uint8, device=dev())

@@ -49,7 +49,7 @@ def test_spill_budget_of_the_hot_kernels(kernels):
     no register lives there).  Still bounded, not zero: the two-workgroups-per-CU instance of the one-chain kernel (256-register
     cap, used from 257 to 703 chains) and the MLP MFMA kernel (128-register cap from two 448-thread workgroups per CU)."""
     clean = ["hmc_gauss_quad_kernel", "hmc_gauss_eig_kernel", "hmc_gauss_wave_eig_kernel", "rmhmc_batch_kernel", "rmhmc_mfma4_kernel",
-             "rmhmc_mfma4x4_kernel", "rmhmc_uv_kernel", "rmhmc_momentum_wave_kernel", "rmhmc_momentum_kernel"]
+             "rmhmc_uv_kernel", "rmhmc_momentum_wave_kernel", "rmhmc_momentum_kernel"]
     for h in clean:
         for k in _find(kernels, h):
             if "rmhmc_uv_kernelILi" in k and "ELb1ELb1E" in k:        # the co-resident instances: next test
@@ -142,7 +142,7 @@ def test_register_budgets_behind_the_occupancy_claims(kernels):
         assert waves(k) >= 2, (k, kernels[k])                      # DESIGN: 2 waves per SIMD at D = 100
     for k in _find(kernels, "rmhmc_batch_kernel"):
         assert waves(k) >= 2, (k, kernels[k])                      # 7 waves of a workgroup on 4 SIMDs
-    for k in _find(kernels, "rmhmc_mfma4_kernel") + _find(kernels, "rmhmc_mfma4x4_kernel"):
+    for k in _find(kernels, "rmhmc_mfma4_kernel"):
         assert waves(k) >= 1 and kernels[k]["lds"] == 0, (k, kernels[k])   # one wave per SIMD, dynamic LDS only
     for k in _find(kernels, "rmhmc_fused_kernelIfLi56ELi1E"):
         assert waves(k) >= 2, (k, kernels[k])                      # __launch_bounds__(256, 2)

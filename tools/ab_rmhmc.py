@@ -1,9 +1,14 @@
 """A/B of the explicit-RMHMC trajectory kernels on cfg3's target (D = 100, L = 10, jitter 1e-3) in ONE process: every argument is
 `<chains>:<key=value,...or ->`; prints steps/s (whole call, HIP events on the current stream), the kernel-only time of the
-profiled launches, the route the library reports and the acceptance rate.  Run through gpurun:
+profiled launches, the route the library reports, the acceptance rate and a SHA-256 of the first call's samples, reject
+counts and final state (two builds of the library compute the same bits iff the digests agree).
 
     python tools/ab_rmhmc.py 256:- 256:rmhmc_uv_co=1 1024:rmhmc_uv_co=1,rmhmc_uv=2
+
+Environment: HTA_LIB (a developer build of the library, path from the repository root), AB_D, AB_L, AB_T (dimension, steps per
+trajectory, trajectories per call; T defaults by chain count), AB_REPS (timed calls, the best counts).
 """
+import hashlib
 import os
 import sys
 
@@ -20,7 +25,7 @@ if os.environ.get("HTA_LIB"):          # a developer build of the library (tools
 
 def main():
     dev = torch.device("cuda:0")
-    D, L, eps, omega, alpha, jitter = 100, int(os.environ.get("AB_L", "10")), 0.1, 10.0, 1e6, 1e-3
+    D, L, eps, omega, alpha, jitter = int(os.environ.get("AB_D", "100")), int(os.environ.get("AB_L", "10")), 0.1, 10.0, 1e6, 1e-3
     g = torch.Generator().manual_seed(0)
     Q = torch.linalg.qr(torch.randn(D, D, generator=g, dtype=torch.float64))[0]
     P = (Q * torch.linspace(0.5, 2.0, D, dtype=torch.float64)) @ Q.T
@@ -31,7 +36,7 @@ def main():
     for combo in sys.argv[1:]:
         cs, tun = combo.split(":", 1)
         C = int(cs)
-        T = 200 if C <= 512 else (100 if C <= 2048 else 50)
+        T = int(os.environ.get("AB_T", "0")) or (200 if C <= 512 else (100 if C <= 2048 else 50))
         _abi.reset_tuning()
         if tun != "-":
             for kv in tun.split(","):
@@ -51,6 +56,9 @@ def main():
         torch.cuda.synchronize()
         first = samples[1:3].cpu().numpy().copy()
         route = _abi.last_route()
+        digest = hashlib.sha256()
+        for x in (samples[1:], rej, cur):
+            digest.update(x.cpu().numpy().tobytes())
         best, kbest = 1e9, 1e9
         for r in range(reps):
             rej.zero_()
@@ -71,8 +79,8 @@ def main():
             dev_note = "  max|d| vs first variant %.2e" % float(np.abs(first - ref[key]).max())
         else:
             ref[key] = first
-        print("chains %5d %-44s %.3e steps/s (call %.3f ms, kernels %.3f ms) acc %.4f  %s%s" % (
-            C, tun, C * T * L / (best * 1e-3), best, kbest, acc, route, dev_note), flush=True)
+        print("chains %5d %-44s %.3e steps/s (call %.3f ms, kernels %.3f ms) acc %.4f  %s  sha256 %s%s" % (
+            C, tun, C * T * L / (best * 1e-3), best, kbest, acc, route, digest.hexdigest()[:16], dev_note), flush=True)
     _abi.reset_tuning()
 
 

@@ -32,7 +32,7 @@ for L, jit in ((10, 1e-3),):
 import ctypes
 lib = ctypes.CDLL(_abi.LIB_PATH)
 if hasattr(lib, "hta_rm_dbg_read"):
-    buf = (ctypes.c_ulonglong * 16)()
+    buf = (ctypes.c_ulonglong * 8)()
     lib.hta_rm_dbg_read(buf)
     names = ["everything else", "-", "-", "refinements + tail | tracked: refresh products", "prologue (publish)", "barrier", "products", "element-wise after products"]
     tot = sum(buf)

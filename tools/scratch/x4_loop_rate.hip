@@ -1,4 +1,4 @@
-// How fast does the product loop of rmhmc_mfma4x4_kernel issue when nothing but the loop runs?  104 instructions of
+// How fast does the product loop of rmhmc_uv_kernel (rows x contraction parity inside a wave) issue when nothing but the loop runs?  104 instructions of
 // v_mfma_f32_4x4x1_16b_f32 (two accumulator chains, operands as in the kernel: 2 x 52 A registers, B from 4 x 2 chunk registers
 // with blgp 4..7), then the parity combine; the result feeds the next round's B values.  Prints counter ticks per product pair.
 //   hipcc --offload-arch=gfx950 -O3 tools/scratch/x4_loop_rate.hip -o tools/scratch/_abl/x4_loop_rate
