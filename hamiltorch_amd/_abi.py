@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhamiltorch_amd.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 MASS_NONE, MASS_DIAG, MASS_FULL = 0, 1, 2
 
@@ -61,6 +61,14 @@ class HtaCbRmhmcArgs(ctypes.Structure):
                 ("accept", c_vp), ("lp_out", c_vp), ("C", ctypes.c_longlong), ("eps", c_f64), ("alpha", c_f64), ("jitter", c_f64),
                 ("omega", c_f64), ("seed", c_u64), ("chain_offset", c_u64), ("L", c_int), ("n_traj", c_int), ("traj_offset", c_int),
                 ("burn", c_int)]
+
+
+class HtaCbRmhmcImpArgs(ctypes.Structure):
+    """csrc/jit/jit_args.h: HtaCbRmhmcImpArgs (the fields of HtaCbRmhmcArgs without omega; iters, thr, max_it)."""
+    _fields_ = [("cur", c_vp), ("init", c_vp), ("samples", c_vp), ("reject_count", c_vp), ("H_old", c_vp), ("H_new", c_vp),
+                ("accept", c_vp), ("lp_out", c_vp), ("iters", c_vp), ("C", ctypes.c_longlong), ("eps", c_f64), ("alpha", c_f64),
+                ("jitter", c_f64), ("thr", c_f64), ("seed", c_u64), ("chain_offset", c_u64), ("L", c_int), ("n_traj", c_int),
+                ("traj_offset", c_int), ("burn", c_int), ("max_it", c_int)]
 
 
 class HtaCbPathArgs(ctypes.Structure):
@@ -124,7 +132,7 @@ PLAIN_SYMBOLS = ["hta_abi_version", "hta_last_error", "hta_device_info", "hta_se
                  "hta_metric_eval_workspace_bytes", "hta_netn_hmc_workspace_bytes",
                  "hta_jit_available", "hta_jit_last_log", "hta_jit_note_fallback", "hta_jit_compile", "hta_jit_free", "hta_jit_load", "hta_jit_unload",
                  "hta_jit_module_info", "hta_jit_hmc_workspace_bytes", "hta_jit_hmc_predraw_bytes", "hta_jit_hmc_sample", "hta_jit_derivs",
-                 "hta_jit_rmhmc_workspace_bytes", "hta_jit_rmhmc_sample", "hta_jit_split_workspace_bytes", "hta_jit_split_sample",
+                 "hta_jit_rmhmc_workspace_bytes", "hta_jit_rmhmc_sample", "hta_jit_rmhmc_implicit_sample", "hta_jit_split_workspace_bytes", "hta_jit_split_sample",
                  "hta_jit_path_leapfrog", "hta_jit_rolled_sample"]
 TYPED_SYMBOLS = sorted(_sig(c_f32).keys())
 
@@ -192,6 +200,7 @@ def load():
         lib.hta_jit_rmhmc_workspace_bytes.argtypes = [c_i64, c_int, c_int]
         lib.hta_jit_rmhmc_workspace_bytes.restype = c_i64
         lib.hta_jit_rmhmc_sample.argtypes = [c_vp, ctypes.POINTER(HtaCbRmhmcArgs), c_int, c_int, c_int, c_vp, c_i64, c_vp]
+        lib.hta_jit_rmhmc_implicit_sample.argtypes = [c_vp, ctypes.POINTER(HtaCbRmhmcImpArgs), c_int, c_int, c_int, c_vp, c_i64, c_vp]
         lib.hta_jit_split_workspace_bytes.argtypes = [c_i64, c_int, c_int]
         lib.hta_jit_split_workspace_bytes.restype = c_i64
         lib.hta_jit_split_sample.argtypes = [c_vp, ctypes.POINTER(HtaCbHmcArgs), c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp]

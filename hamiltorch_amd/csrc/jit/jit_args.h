@@ -15,6 +15,8 @@
 #define HTA_CB_SET_PATH 5   /* hta_cb_path_kernel | hta_cb_split_path_kernel (info[6] = M | 0): leapfrog paths */
 #define HTA_CB_SET_ROLLED 6 /* hta_cb_rolled_kernel: plain HMC on a callable rolled over its data rows (info[6] = U, info[7] = groups) */
 #define HTA_CB_SET_RMHMC_HESS 7 /* hta_cb_rmhmc_hess_kernel: explicit RMHMC trajectories with Metric.HESSIAN, D <= 16 (HtaCbRmhmcArgs, alpha unread) */
+#define HTA_CB_SET_RMHMC_IMP 8      /* hta_cb_rmhmc_imp_kernel: implicit RMHMC trajectories (soft-abs), D <= 16 (HtaCbRmhmcImpArgs)           */
+#define HTA_CB_SET_RMHMC_IMP_HESS 9 /* hta_cb_rmhmc_imp_hess_kernel: the same with Metric.HESSIAN (alpha unread)                             */
 
 /* HTA_CB_METRIC of a generated include made for an RMHMC trajectory kernel: the values of HTA_METRIC_* in include/hamiltorch_amd.h */
 #define HTA_CB_METRIC_HESSIAN 0
@@ -92,6 +94,37 @@ typedef struct HtaCbRmhmcArgs {
   unsigned long long seed, chain_offset;
   int L, n_traj, traj_offset, burn;
 } HtaCbRmhmcArgs;
+
+/* hta_jit_rmhmc_implicit_sample (csrc/jit/rmhmc_implicit_callback.hip.in): the generalised leapfrog with fixed-point iterations.  A block
+ * of its own - the explicit kernels' kernarg block does not change: the fields of HtaCbRmhmcArgs without omega, then the fixed-point rule. */
+typedef struct HtaCbRmhmcImpArgs {
+  void* cur;             /* [C, D] current state, in / out                                     */
+  const void* init;      /* [C, D] params_init (Q2 reset)                                      */
+  void* samples;         /* [S, C, D] or NULL                                                  */
+  int* reject_count;     /* [C]                                                                */
+  void* H_old;           /* [C] of the launch's last trajectory, or NULL                       */
+  void* H_new;
+  unsigned char* accept;
+  void* lp_out;          /* [C] log p at the state the launch ended in, or NULL                */
+  int* iters;            /* [C] or NULL: += the fixed-point iterations the chain executed while active, both loops (tests) */
+  long long C;
+  double eps, alpha, jitter;
+  double thr;            /* fixed_point_threshold: a chain leaves a loop once max_j (state_j - new_j)^2 < thr (compared in double) */
+  unsigned long long seed, chain_offset;
+  int L, n_traj, traj_offset, burn;
+  int max_it;            /* fixed_point_max_iterations: the trip count of each loop at most; fixes the jitter sub-stream layout */
+} HtaCbRmhmcImpArgs;
+
+#ifdef __cplusplus
+static_assert(sizeof(HtaCbRmhmcArgs) == 136, "HtaCbRmhmcArgs");
+static_assert(sizeof(HtaCbRmhmcImpArgs) == 152 && __builtin_offsetof(HtaCbRmhmcImpArgs, iters) == 64 &&
+                  __builtin_offsetof(HtaCbRmhmcImpArgs, C) == 72 && __builtin_offsetof(HtaCbRmhmcImpArgs, thr) == 104 &&
+                  __builtin_offsetof(HtaCbRmhmcImpArgs, seed) == 112 && __builtin_offsetof(HtaCbRmhmcImpArgs, L) == 128 &&
+                  __builtin_offsetof(HtaCbRmhmcImpArgs, max_it) == 144,
+              "HtaCbRmhmcImpArgs");
+#else
+_Static_assert(sizeof(HtaCbRmhmcImpArgs) == 152, "HtaCbRmhmcImpArgs");
+#endif
 
 /* hta_jit_path_leapfrog (csrc/jit/path_callback.hip.in): every step of one leapfrog call, nothing drawn, nothing decided */
 typedef struct HtaCbPathArgs {

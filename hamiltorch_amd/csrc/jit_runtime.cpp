@@ -115,6 +115,8 @@ const struct KernelSet {
     {HTA_CB_SET_PATH, "hta_cb_path_kernel", &Module::path, nullptr, nullptr},          // a list (info[6] = M > 0): hta_cb_split_path_kernel
     {HTA_CB_SET_ROLLED, "hta_cb_rolled_kernel", &Module::rolled, "hta_cb_predraw_kernel", &Module::predraw},
     {HTA_CB_SET_RMHMC_HESS, "hta_cb_rmhmc_hess_kernel", &Module::rmhmc, nullptr, nullptr},
+    {HTA_CB_SET_RMHMC_IMP, "hta_cb_rmhmc_imp_kernel", &Module::rmhmc, nullptr, nullptr},
+    {HTA_CB_SET_RMHMC_IMP_HESS, "hta_cb_rmhmc_imp_hess_kernel", &Module::rmhmc, nullptr, nullptr},
 };
 
 const KernelSet* kernel_set(int set) {
@@ -447,6 +449,35 @@ int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int it
   note_route("%s<D=%d,%s,jitter=%d,nodes=%d+%d>", k->name, D, dtype_name(itemsize), has_jitter ? 1 : 0, m->info[5], m->info[6]);
   profile_begin((hipStream_t)stream);
   const int rc = launch(m->rmhmc, "hta_jit_rmhmc_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
+  profile_end((hipStream_t)stream);
+  return rc;
+}
+
+/* Implicit RMHMC trajectories (the generalised leapfrog with fixed-point iterations) on a compiled callable: the module holds the
+ * soft-abs kernel (HTA_CB_SET_RMHMC_IMP) or the Metric.HESSIAN one (HTA_CB_SET_RMHMC_IMP_HESS, args->alpha unread). */
+int hta_jit_rmhmc_implicit_sample(void* module, const HtaCbRmhmcImpArgs* args, int D, int itemsize, int has_jitter, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+  using namespace hta;
+  Module* m = (Module*)module;
+  const KernelSet* k = kernel_set(m && m->info[4] == HTA_CB_SET_RMHMC_IMP_HESS ? HTA_CB_SET_RMHMC_IMP_HESS : HTA_CB_SET_RMHMC_IMP);
+  // (the checks that need neither a module nor a device come first: they hold on a machine without a GPU too)
+  HTA_REQUIRE(args && args->cur && args->init && args->reject_count && args->C > 0 && args->L >= 0 && args->n_traj >= 0,
+              "hta_jit_rmhmc_implicit_sample: bad arguments");
+  HTA_REQUIRE(args->max_it >= 0, "hta_jit_rmhmc_implicit_sample: max_it = %d (fixed_point_max_iterations >= 0)", args->max_it);
+  HTA_REQUIRE(args->thr == args->thr, "hta_jit_rmhmc_implicit_sample: thr is NaN (fixed_point_threshold)");
+  // (the jitter sub-streams of a trajectory are 32-bit positions: 2 + L (2 max_it + 2) of them)
+  HTA_REQUIRE(3 + (int64_t)args->L * (2 * (int64_t)args->max_it + 2) < (int64_t)1 << 31,
+              "hta_jit_rmhmc_implicit_sample: L (2 max_it + 2) = %lld sub-streams per trajectory", (long long)args->L * (2 * (long long)args->max_it + 2));
+  HTA_REQUIRE(workspace && workspace_bytes >= hta_jit_rmhmc_workspace_bytes(args->C, D, itemsize),
+              "hta_jit_rmhmc_implicit_sample: workspace of %lld bytes, %lld needed (hta_jit_rmhmc_workspace_bytes)", (long long)workspace_bytes,
+              (long long)hta_jit_rmhmc_workspace_bytes(args->C, D, itemsize));
+  if (int rc = check_module(m, "hta_jit_rmhmc_implicit_sample", D, itemsize, has_jitter ? 1 : 0, k->set)) return rc;
+  if (args->n_traj == 0) return HTA_OK;
+  HtaCbRmhmcImpArgs a = *args;
+  a.lp_out = workspace;
+  note_route("%s<D=%d,%s,jitter=%d,nodes=%d+%d>", k->name, D, dtype_name(itemsize), has_jitter ? 1 : 0, m->info[5], m->info[6]);
+  profile_begin((hipStream_t)stream);
+  const int rc = launch(m->rmhmc, "hta_jit_rmhmc_implicit_sample", a.C, &a, sizeof(a), (hipStream_t)stream);
   profile_end((hipStream_t)stream);
   return rc;
 }

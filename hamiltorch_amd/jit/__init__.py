@@ -145,7 +145,19 @@ class CompiledRolled(CompiledHMC):
 
 
 class CompiledDerivs(CompiledHMC):
-    """A traced callable compiled into the derivative kernels of the Riemannian samplers (csrc/jit/derivs_callback.hip.in)."""
+    """A traced callable compiled into the derivative kernels of the Riemannian samplers (csrc/jit/derivs_callback.hip.in) - or, with a
+    generated include made for a metric, into the explicit-RMHMC trajectory kernel; `implicit()`: the implicit integrator's kernel
+    around the SAME include (csrc/jit/rmhmc_implicit_callback.hip.in), a module of its own, built when first asked for."""
+
+    _implicit = None
+
+    def implicit(self):
+        if self.skeleton != runtime.SKELETON_RMHMC:
+            raise Unsupported("the implicit-RMHMC trajectory kernel is built around an RMHMC include only")
+        if self._implicit is None:
+            key, blob = runtime.compile_source(self.generated, runtime.SKELETON_RMHMC_IMPLICIT)
+            self._implicit = CompiledPath(self.traced, key, blob, self.dtype, self.mass_kind)
+        return self._implicit
 
 
 def compile_hmc(fn, example, dtype, mass_kind, fresh=False):
@@ -163,16 +175,20 @@ def compile_derivs(fn, example, dtype, fresh=False):
 _RMHMC_KINDS = {"rmhmc": ("softabs", False), "rmhmc-jitter": ("softabs", True), "rmhmc-hess": ("hessian", False), "rmhmc-hess-jitter": ("hessian", True)}
 
 
-def compile_rmhmc(fn, example, dtype, jitter, fresh=False, metric="softabs"):
+def compile_rmhmc(fn, example, dtype, jitter, fresh=False, metric="softabs", integrator="explicit"):
     """The callable built into the explicit-RMHMC trajectory kernel (csrc/jit/rmhmc_callback.hip.in; D <= 16) under `metric`
-    ("softabs": rmhmc_metric_softabs.inc, "hessian": rmhmc_metric_hessian.inc); raises ``Unsupported``."""
+    ("softabs": rmhmc_metric_softabs.inc, "hessian": rmhmc_metric_hessian.inc); raises ``Unsupported``.  integrator="implicit": the
+    implicit integrator's kernel (csrc/jit/rmhmc_implicit_callback.hip.in) around the same trace, checks and generated include - a
+    callable already traced for one integrator is not traced again for the other, only the other module is built."""
     if (metric, bool(jitter)) not in _RMHMC_KINDS.values():
         raise ValueError("compile_rmhmc: metric is 'softabs' or 'hessian', got %r" % (metric,))
+    if integrator not in ("explicit", "implicit"):
+        raise ValueError("compile_rmhmc: integrator is 'explicit' or 'implicit', got %r" % (integrator,))
     if example.numel() > runtime.MAX_RMHMC_DIM:
         _note("D = %d: the chain-per-lane Riemannian kernel holds a chain's matrices in registers (D <= %d)" % (example.numel(), runtime.MAX_RMHMC_DIM))
         raise Unsupported(last_reason())
     kind = next(k for k, v in _RMHMC_KINDS.items() if v == (metric, bool(jitter)))
-    return _compile(fn, example, dtype, kind, fresh)
+    return _compile(fn, example, dtype, kind, fresh, path="implicit" if integrator == "implicit" else False)
 
 
 def compile_path(fn_or_list, example, dtype, mass_kind, fresh=False):
@@ -187,10 +203,13 @@ def compile_path(fn_or_list, example, dtype, mass_kind, fresh=False):
 
 
 def _finish(out, path):
-    """Build the code object the caller asked for (the trajectory kernel's, or the path kernel's) around a compiled entry.  hipRTC turning
+    """Build the code object the caller asked for (the trajectory kernel's, the path kernel's, or - path = "implicit" - the
+    implicit-RMHMC kernel's) around a compiled entry.  hipRTC turning
     the generated text down (an emitter bug, a device function hipRTC lacks) is not the user's problem: the callable runs on the
     previous path, the reason (the compiler's first error line) is reported like any other refusal."""
     try:
+        if path == "implicit":
+            return out.implicit()
         if path:
             return out.path()
         out._built()
@@ -205,7 +224,7 @@ def _compile(fn, example, dtype, mass_kind, fresh, path=False):
     # (the rolling switches are part of the key: an entry made under one setting is not handed out under another)
     # ('force' rolls for sample() what it keeps straight-line for leapfrog(): there the two callers do not share an entry)
     cfg = (int(example.numel()), dtype, mass_kind, example.device.type, runtime.roll_mode(), runtime.rolled_table_mode(),
-           bool(path) and runtime.roll_mode() == "force")
+           path is True and runtime.roll_mode() == "force")
     sig = objs = None
     try:
         sig, objs = _signature(fn)

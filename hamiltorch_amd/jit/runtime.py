@@ -28,6 +28,7 @@ SKELETON_PATH = "jit/path_callback.hip.in"
 SKELETON_ROLLED = "jit/rolled_callback.hip.in"
 SKELETON_DERIVS = "jit/derivs_callback.hip.in"
 SKELETON_RMHMC = "jit/rmhmc_callback.hip.in"      # both metrics: HTA_CB_METRIC of the generated include picks rmhmc_metric_*.inc
+SKELETON_RMHMC_IMPLICIT = "jit/rmhmc_implicit_callback.hip.in"      # the implicit integrator over the same include and metric files
 # (SLP vectorisation ON: the straight-line callback code packs into v_pk_mul / v_pk_fma pairs - 67 -> 59 instructions per
 #  leapfrog step of the notebook funnel, tools/jit_isa.py; -ffp-contract=fast fuses across the generated statements)
 OPTIONS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast")
@@ -460,6 +461,29 @@ def rmhmc_sample(module, cur, init, L, eps, alpha, jitter, omega, n_traj, traj_o
         _abi._check(_abi.load().hta_jit_rmhmc_sample(module.handle, ctypes.byref(a), D, cur.element_size(), 0 if jitter is None else 1,
                                                      workspace.data_ptr(), workspace.numel() * workspace.element_size(),
                                                      _abi._stream(cur)), "hta_jit_rmhmc_sample")
+
+
+def rmhmc_implicit_sample(module, cur, init, L, eps, alpha, jitter, thr, max_it, n_traj, traj_offset, burn, seed, chain_offset, samples,
+                          reject_count, workspace, iters=None):
+    """hta_jit_rmhmc_implicit_sample: implicit RMHMC trajectories [traj_offset, traj_offset + n_traj) on the compiled callable, under the
+    metric the module was built for (SKELETON_RMHMC_IMPLICIT).  `iters` (int32 [C], tests): accumulates the fixed-point iterations every
+    chain executed while active."""
+    _abi.require_device(cur, "params")
+    C, D = cur.shape
+    a = _abi.HtaCbRmhmcImpArgs()
+    a.cur, a.init = cur.data_ptr(), _abi._p(init, cur).value
+    a.samples = None if samples is None else _abi._p(samples, cur).value
+    a.reject_count = reject_count.data_ptr()
+    a.iters = None if iters is None else iters.data_ptr()
+    a.C, a.eps, a.alpha = C, float(eps), 0.0 if alpha is None else float(alpha)
+    a.jitter = 0.0 if jitter is None else float(jitter)
+    a.thr, a.max_it = float(thr), int(max_it)
+    a.seed, a.chain_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_offset)
+    a.L, a.n_traj, a.traj_offset, a.burn = int(L), int(n_traj), int(traj_offset), int(burn)
+    with torch.cuda.device(cur.device):
+        _abi._check(_abi.load().hta_jit_rmhmc_implicit_sample(module.handle, ctypes.byref(a), D, cur.element_size(), 0 if jitter is None else 1,
+                                                              workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                                              _abi._stream(cur)), "hta_jit_rmhmc_implicit_sample")
 
 
 def _deriv_call(module, a, which, like):

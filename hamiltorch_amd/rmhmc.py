@@ -642,13 +642,90 @@ def implicit_leapfrog(params, momentum, log_prob_func, steps, step_size, jitter,
     return [unb(t) for t in pt.unbind(0)], [unb(t) for t in pp.unbind(0)]
 
 
-def sample_implicit(log_prob_func, theta0, N, L, eps, burn, jitter, alpha, metric, thr, max_it, seed, chain_offset, verbose):
-    """The RMHMC / IMPLICIT branch of sample() (S:969-1026): gibbs (sub-stream 0), H_old (1), L implicit steps
-    (2 ..), H_new (2 + L * (2 max_it + 2)), Metropolis select + bookkeeping in `hta_mh_select`."""
+def implicit_compiled_enabled():
+    """HAMILTORCH_AMD_JIT_IMPLICIT=0 keeps sample(RMHMC, IMPLICIT) on the launch sequence (the parity partner of the compiled kernel)."""
+    return os.environ.get("HAMILTORCH_AMD_JIT_IMPLICIT", "1") != "0"
+
+
+def _sample_implicit_compiled(log_prob_func, theta0, N, L, eps, burn, jitter, alpha, kind, thr, max_it, seed, chain_offset, verbose):
+    """The whole run inside the compiled chain-per-lane kernel of the implicit integrator (csrc/jit/rmhmc_implicit_callback.hip.in with
+    rmhmc_metric_softabs.inc or rmhmc_metric_hessian.inc) when the callback compiler covers the callable: D <= 16.  The twin of
+    _sample_explicit_compiled: None = not applicable (the reason is in hta_last_route()); the result is checked against the callable
+    itself on the states the run ended in, a mismatch re-traces once and else returns None."""
+    from . import jit
+    from .samplers import _num_rows
+    C, D = theta0.shape
+    metric = {_abi.METRIC_SOFTABS: "softabs", _abi.METRIC_HESSIAN: "hessian"}.get(kind)
+    why = ("HAMILTORCH_AMD_JIT=0" if not jit.enabled() else
+           "HAMILTORCH_AMD_JIT_IMPLICIT=0" if not implicit_compiled_enabled() else
+           "log_prob_func is not a callable" if not callable(log_prob_func) else
+           "the metric has no compiled implicit kernel" if metric is None else
+           "fixed_point_max_iterations < 0 or fixed_point_threshold is NaN" if int(max_it) < 0 or thr != thr else None)
+    if why is not None or not theta0.is_cuda:
+        if theta0.is_cuda:
+            _abi.load().hta_jit_note_fallback(why.encode())
+        return None
+    for fresh in (False, True):
+        hits = jit.stats["trace_hits"]
+        try:
+            comp = jit.compile_rmhmc(log_prob_func, theta0[0], theta0.dtype, jitter is not None, fresh=fresh, metric=metric,
+                                     integrator="implicit")
+        except jit.Unsupported as e:
+            _abi.load().hta_jit_note_fallback(str(e)[:140].encode("utf-8", "replace"))
+            return None
+        reused = jit.stats["trace_hits"] > hits
+        module = comp.module(theta0.device)
+        S = _num_rows(N, burn)
+        samples = torch.empty((S, C, D), dtype=theta0.dtype, device=theta0.device)
+        cur = torch.empty_like(theta0)
+        rejected = torch.empty(C, dtype=torch.int32, device=theta0.device)
+        _abi.run_begin(theta0, cur, samples[0], rejected)
+        ws = torch.empty(jit.runtime.rmhmc_workspace_bytes(C, D, theta0.element_size()), dtype=torch.uint8, device=theta0.device)
+        prog = util._Progress('Sampling (Sampler.RMHMC; Integrator.IMPLICIT)', N, verbose)
+        chunk = max(1, -(-N // 20)) if verbose else N
+        for start in range(0, N, chunk):
+            k = min(chunk, N - start)
+            jit.runtime.rmhmc_implicit_sample(module, cur, theta0, L, eps, alpha, jitter, thr, max_it, k, start, burn, seed, chain_offset,
+                                              samples, rejected, ws)
+            prog.update(start + k - 1)
+        prog.end()
+        if os.environ.get("HAMILTORCH_AMD_JIT_VERIFY", "1") == "0" or N == 0:
+            return samples, rejected
+        kk = min(C, 128)
+        mine = ws[:C * theta0.element_size()].view(theta0.dtype)[:kk]
+        ref = jit.torch_logp(log_prob_func, cur[:kk]).to(mine.dtype).reshape(-1)
+        fa, fb = torch.isfinite(mine), torch.isfinite(ref)
+        tol = 2e-4 if mine.dtype == torch.float32 else 1e-9
+        if bool(((fa == fb) & (((mine - ref).abs() <= tol * (10.0 + ref.abs())) | ~fb)).all()):
+            return samples, rejected
+        if not reused:
+            break
+    import warnings
+    warnings.warn("hamiltorch_amd: the compiled form of %r disagrees with the callable itself on the sampled states; re-running "
+                  "on the launch-per-evaluation path" % (log_prob_func,))
+    _abi.load().hta_jit_note_fallback(b"compiled code disagrees with the callable")
+    return None
+
+
+def sample_implicit(log_prob_func, theta0, N, L, eps, burn, jitter, alpha, metric, thr, max_it, seed, chain_offset, verbose, native=True):
+    """The RMHMC / IMPLICIT branch of sample() (S:969-1026): the compiled trajectory kernel where it applies (_sample_implicit_compiled;
+    native=False, HAMILTORCH_AMD_JIT=0 and HAMILTORCH_AMD_JIT_IMPLICIT=0 skip it), else one launch per evaluation: gibbs (sub-stream 0),
+    H_old (1), L implicit steps (2 ..), H_new (2 + L * (2 max_it + 2)), Metropolis select + bookkeeping in `hta_mh_select`."""
     from .samplers import _num_rows
     kind = _metric_kind(metric)
     if alpha is None and kind == _abi.METRIC_SOFTABS:
         raise TypeError("softabs_const must be set for Metric.SOFTABS")
+    # why the compiled kernel did not take the run: noted again after the launch sequence, so that hta_last_route() ends on it
+    reason = None
+    if not native:
+        reason = "native=False"
+    else:
+        out = _sample_implicit_compiled(log_prob_func, theta0, N, L, eps, burn, jitter, alpha, kind, thr, max_it, seed, chain_offset, verbose)
+        if out is not None:
+            return out
+        route = _abi.last_route() if theta0.is_cuda else ""
+        if "(not compiled: " in route:
+            reason = route.split("(not compiled: ", 1)[1].rsplit(")", 1)[0]
     C, D = theta0.shape
     dt, dev = theta0.dtype, theta0.device
     cv = _curvature_for(log_prob_func, theta0)
@@ -688,4 +765,6 @@ def sample_implicit(log_prob_func, theta0, N, L, eps, burn, jitter, alpha, metri
         lp0 = None if fresh else torch.where(took, lp1, lp0)
         prog.update(n)
     prog.end()
+    if reason is not None:
+        _abi.load().hta_jit_note_fallback(reason[:140].encode("utf-8", "replace"))
     return samples, rejected

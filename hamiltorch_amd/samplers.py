@@ -585,7 +585,7 @@ def sample(log_prob_func, params_init, num_samples=10, num_steps_per_sample=10, 
             from . import rmhmc
             samples, rejected = rmhmc.sample_implicit(log_prob_func, theta0, num_samples, num_steps_per_sample, step_size,
                                                       burn_k, jitter, softabs_const, metric, fixed_point_threshold,
-                                                      fixed_point_max_iterations, seed, chain_offset, verbose)
+                                                      fixed_point_max_iterations, seed, chain_offset, verbose, native)
         elif sampler == Sampler.RMHMC:
             raise NotImplementedError("Integrator.S3 (semi-separable Hamiltonians through a user ham_func) is outside "
                                       "the accelerated path")

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HTA_ABI_VERSION 14
+#define HTA_ABI_VERSION 15
 
 #define HTA_OK 0
 #define HTA_ERR_INVALID (-1)   /* bad argument                           */
@@ -494,6 +494,13 @@ int hta_jit_derivs(void* module, const HtaCbDerivArgs* args, int which, int D, i
 int64_t hta_jit_rmhmc_workspace_bytes(int64_t C, int D, int itemsize);
 int hta_jit_rmhmc_sample(void* module, const HtaCbRmhmcArgs* args, int D, int itemsize, int has_jitter, void* workspace,
                          int64_t workspace_bytes, void* stream);
+/* Implicit RMHMC (the generalised leapfrog with fixed-point iterations, S:305-387, inside the RMHMC branch of sample(), S:969-1026;
+ * Metric.SOFTABS or Metric.HESSIAN by the module's kernel set) for a general target of small dimension (D <= 16) on a compiled
+ * callable: trajectories [traj_offset, traj_offset + n_traj), a chain per lane, up to 3 + L (2 max_it + 2) metric evaluations per
+ * trajectory in the lane's registers; a chain leaves a fixed-point loop by the break rule of S:336-338 / S:356-358, a wave when none
+ * of its chains is left - csrc/jit/rmhmc_implicit_callback.hip.in.  args->max_it >= 0, args->thr not NaN; `workspace` as above. */
+int hta_jit_rmhmc_implicit_sample(void* module, const HtaCbRmhmcImpArgs* args, int D, int itemsize, int has_jitter, void* workspace,
+                                  int64_t workspace_bytes, void* stream);
 
 /* measurement knobs: "small_chains_per_block" (launch shape of the thread-per-chain kernel), "fill_blocks" (grid cap of the
  * pre-draw pass of the Gaussian path: 256-thread blocks, grid-stride; 4096),
