@@ -1384,8 +1384,14 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
 // The row wave of an integrating wave (ROWS above): same lane, same chain, same coordinate.  It walks the groups of trajectories in
 // the integrator's order, one barrier in front of each, and owns the output side.  In the burn-in phase it stores no row (the
 // one-launch form rewrites the chain's slot of `theta` every trajectory; nobody reads those within the launch): only the final state.
+// WT (tuning key "quad_rows_wt", the local and wide launches): the sample row element is stored WRITE-THROUGH at agent scope (a relaxed
+// atomic store: global_store_dword ... sc1, a store the compiler tracks), so a launch's 12 MB of rows leave the XCD's L2 while the
+// launch runs, not in the write-back of dirty lines behind its last wave (profiles/r15a_quad_lead.txt).  Same value, same address;
+// the final state, the reject count and a starved launch's NaN rows stay plain stores.  -DQUAD_ABLATE_ROWSTORE (developer builds,
+// timing only, wrong samples): the row wave stores no sample row - the ceiling of WT.
 template <int D, int LB, bool LOCAL = false, bool WIDE = false>
-__device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t gt, uint32_t lds) {
+__device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t gt, uint32_t lds,
+                                               const bool wt = false) {
   typedef float T;
   constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
   const bool on = (gt >> 2) < a.C;
@@ -1418,7 +1424,17 @@ __device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const 
     qc = acc ? q : qc;
     accepted += acc ? 1 : 0;
     if (q2 && !acc) qc = a.theta_init[el];       // Q2: back to params_init itself
-    if (row) { if (on) row[el] = qc; row += C * D; }
+#if defined(QUAD_ABLATE_ROWSTORE)
+    if (row) row += C * D;
+#else
+    if (row) {
+      if (on) {
+        if (wt) __hip_atomic_store(row + el, qc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else row[el] = qc;
+      }
+      row += C * D;
+    }
+#endif
   };
   auto group = [&](auto G, bool q2) {
     asm volatile("s_barrier" ::: "memory");      // the integrator has filled this buffer
@@ -1609,27 +1625,40 @@ __global__ __launch_bounds__(quad_fused_threads(NI)) void hmc_gauss_quad_fused_k
 // only, wrong samples: profiles/r08a_quad_local.txt): the producer waves draw nothing - the ceiling of the integrator's side.
 // WIDE (quad_body: WIDE): element k of the record of position p goes to the integrating lane chain * 4 + k of block p >> 2, slot p & 3 -
 // four dwords 16 bytes apart; a sweep of eight positions is two blocks.
+// The sweep: lane `pl` of `nl` producer lanes draws positions pl / 16, + nl / 16, ... of a group for chain pl % 16 (128 lanes: eight
+// positions of 16 chains per sweep); pl < 0: this wave draws nothing and only walks the groups.
+// LEAD (hmc_gauss_quad_lead_kernel, tuning key "quad_lead"): the groups up to and including the launch's first full pass of NU are
+// drawn with the sweep (pl_lead, nl_lead) - more lanes: the integrating wave waits for exactly these records with nothing to do -
+// and the groups behind it with (pl, nl); both sweeps put a record where the integrating wave reads it.  pl_lead % 16 == pl % 16.
+// INVARIANT: which lanes draw is the only thing a sweep decides.  Every wave that runs this function - drawing or not, chains past
+// a.C or not, a launch shorter than one group or not - executes one "s_waitcnt lgkmcnt(0) ; s_barrier" per group of
+// quad_local_groups, in that order, and the two closing barriers: the barrier sequence of every role is a function of the launch
+// arguments alone, whatever the sweeps are.
 template <int D, int LB, bool WIDE = false>
 __device__ __forceinline__ void quad_local_produce(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t c0, const uint32_t recl,
-                                                   const int pl) {
+                                                   const int pl, const int nl, const int pl_lead, const int nl_lead) {
   constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
   static_assert(rec_elems<float, D>() == 4, "one 16-byte record");
   typedef float V4f __attribute__((ext_vector_type(4)));
   typedef __attribute__((address_space(3))) V4f* lvec_t;
   typedef __attribute__((address_space(3))) float* lflt_t;
   (void)(lvec_t)nullptr;
-  const int chain = pl & 15, p0 = pl >> 4;                                      // 128 lanes: eight positions of 16 chains per sweep
+  const int chain = pl_lead & 15;
   const int64_t c = min(c0 + chain, a.C - 1);                                   // (past a.C: the last chain again, as the integrator does)
   const uint64_t gchain = a.chain_offset + (uint64_t)c;
-  uint32_t dst = recl + (WIDE ? (uint32_t)((p0 >> 2) * 1024 + chain * 64 + (p0 & 3) * 4) : (uint32_t)(p0 * 256 + chain * 16));
-  const uint32_t dst_both = 2u * dst + (uint32_t)(NU * 256);
+  uint32_t buf = recl;                                                          // the record buffer being filled
+  const uint32_t buf_both = 2u * recl + (uint32_t)(NU * 256);
+  bool lead = true;
   quad_local_groups<NS, NU>(a, [&](int t0, int, auto G, auto) {
 #if !defined(QUAD_ABLATE_LOCAL)
-    for (int p = p0; p < decltype(G)::value; p += 8) {
+    const int l = lead ? pl_lead : pl, step = (lead ? nl_lead : nl) >> 4;       // (step: a multiple of four positions - whole blocks of WIDE)
+    const int p0 = l >= 0 ? l >> 4 : NU;                                        // (NU: past every group)
+    const uint32_t dst = buf + (WIDE ? (uint32_t)((p0 >> 2) * 1024 + chain * 64 + (p0 & 3) * 4) : (uint32_t)(p0 * 256 + chain * 16));
+    for (int p = p0; p < decltype(G)::value; p += step) {                       // (p < NU: inside the buffer)
       float rec[4];
       quad_make_record<D>(a.seed, gchain, (uint32_t)(a.traj_offset + t0 + p), eig, rec);
       if constexpr (WIDE) {
-        const lflt_t w = (lflt_t)(uintptr_t)(dst + (uint32_t)((p - p0) * 256));      // (eight positions on: two blocks of 1024 bytes)
+        const lflt_t w = (lflt_t)(uintptr_t)(dst + (uint32_t)((p - p0) * 256));      // (four positions on: one block of 1024 bytes)
         w[0] = rec[0]; w[4] = rec[1]; w[8] = rec[2]; w[12] = rec[3];
       } else {
         *(lvec_t)(uintptr_t)(dst + (uint32_t)((p - p0) * 256)) = V4f{rec[0], rec[1], rec[2], rec[3]};
@@ -1637,12 +1666,13 @@ __device__ __forceinline__ void quad_local_produce(const GaussArgs<float>& a, co
     }
 #endif
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // publishes this group's records
-    dst = dst_both - dst;
+    buf = buf_both - buf;
+    if (decltype(G)::value == NU) lead = false;
   });
   asm volatile("s_barrier\n\ts_barrier" ::: "memory");                          // the last group's hand-over and the status message: the other roles'
 }
 template <int D, int LB>
-__global__ __launch_bounds__(256) void hmc_gauss_quad_local_kernel(GaussArgs<float> a, const float* __restrict__ eig) {
+__global__ __launch_bounds__(256) void hmc_gauss_quad_local_kernel(GaussArgs<float> a, const float* __restrict__ eig, int wt) {
   constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
   __shared__ __attribute__((aligned(16))) float ring[2 * NU * 64 + 2 * NU * 64];      // messages (64 lanes x 4 bytes) | records (16 chains x 16 bytes), two passes each
   const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
@@ -1652,14 +1682,21 @@ __global__ __launch_bounds__(256) void hmc_gauss_quad_local_kernel(GaussArgs<flo
     __builtin_amdgcn_s_setprio(3);
     quad_body<D, false, LB, 7, true, true, true>(a, eig, gt, QuadFused{nullptr, 1, 0u, 0, nullptr, 0}, msgs + (uint32_t)lane * (QUAD_ABLATE_WIDE_ON ? 16u : 4u), recs + (uint32_t)lane * (QUAD_ABLATE_WIDE_ON ? 16u : 4u));
   }
-  else if (wave == 1) quad_rows_body<D, LB, true>(a, eig, gt, msgs + (uint32_t)lane * 4u);
-  else quad_local_produce<D, LB>(a, eig, (int64_t)blockIdx.x * 16, recs, (int)threadIdx.x - 128);
+  else if (wave == 1) quad_rows_body<D, LB, true>(a, eig, gt, msgs + (uint32_t)lane * 4u, wt != 0);
+  else quad_local_produce<D, LB>(a, eig, (int64_t)blockIdx.x * 16, recs, (int)threadIdx.x - 128, 128, (int)threadIdx.x - 128, 128);
 }
 // WIDE (tuning key "quad_wide"): the local launch - the same roles, rings of the same sizes, the same groups and barriers - with
 // 16-byte hand-overs per block of four positions (quad_body: WIDE); a lane's base in a block of either ring is lane x 16 bytes.
 // Results are bit-identical to the local launch (tests/test_gpu_quad_wide.py).
-template <int D, int LB>
-__global__ __launch_bounds__(256) void hmc_gauss_quad_wide_kernel(GaussArgs<float> a, const float* __restrict__ eig) {
+// LEAD (tuning key "quad_lead", hmc_gauss_quad_lead_kernel): the wide launch with 512 threads.  The launch's lead-in is the time the
+// producers need for the first full pass - 32 positions x 16 chains, four sweeps of waves 2-3 - while the integrating wave, done
+// with the lead group after one eighth of that, and the row wave stand at a barrier.  Waves 4-7 draw their share of the groups
+// up to and including that pass (quad_local_produce: LEAD): 384 lanes, 24 positions per sweep, waves 4-5 (the SIMDs of the two
+// idle roles) first in the sweep, so the pass is two wave-sweeps on each SIMD instead of four on two.  Behind it they draw
+// nothing and walk the groups to the end with everybody's barriers; they never leave early.  Same records in the same places:
+// results are bit-identical to the 256-thread launch (tests/test_gpu_quad_lead.py).
+template <int D, int LB, bool LEAD>
+__device__ __forceinline__ void quad_wide_block(const GaussArgs<float>& a, const float* __restrict__ eig, const bool wt) {
   constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
   static_assert(NS == 4 && NU % 4 == 0, "groups are whole blocks of four positions, or single ones");
   __shared__ __attribute__((aligned(16))) float ring[2 * NU * 64 + 2 * NU * 64];      // as the local launch's: messages | records, two passes each
@@ -1670,8 +1707,20 @@ __global__ __launch_bounds__(256) void hmc_gauss_quad_wide_kernel(GaussArgs<floa
     __builtin_amdgcn_s_setprio(3);
     quad_body<D, false, LB, 7, true, true, true, true>(a, eig, gt, QuadFused{nullptr, 1, 0u, 0, nullptr, 0}, msgs + (uint32_t)lane * 16u, recs + (uint32_t)lane * 16u);
   }
-  else if (wave == 1) quad_rows_body<D, LB, true, true>(a, eig, gt, msgs + (uint32_t)lane * 16u);
-  else quad_local_produce<D, LB, true>(a, eig, (int64_t)blockIdx.x * 16, recs, (int)threadIdx.x - 128);
+  else if (wave == 1) quad_rows_body<D, LB, true, true>(a, eig, gt, msgs + (uint32_t)lane * 16u, wt);
+  else if constexpr (LEAD) {
+    const int lw = wave < 4 ? wave : (wave < 6 ? wave - 4 : wave - 2);               // place in the lead sweep: waves 4 5 2 3 6 7
+    quad_local_produce<D, LB, true>(a, eig, (int64_t)blockIdx.x * 16, recs, wave < 4 ? (int)threadIdx.x - 128 : -1, 128, lw * 64 + lane, 384);
+  }
+  else quad_local_produce<D, LB, true>(a, eig, (int64_t)blockIdx.x * 16, recs, (int)threadIdx.x - 128, 128, (int)threadIdx.x - 128, 128);
+}
+template <int D, int LB>
+__global__ __launch_bounds__(256) void hmc_gauss_quad_wide_kernel(GaussArgs<float> a, const float* __restrict__ eig, int wt) {
+  quad_wide_block<D, LB, false>(a, eig, wt != 0);
+}
+template <int D, int LB>
+__global__ __launch_bounds__(512) void hmc_gauss_quad_lead_kernel(GaussArgs<float> a, const float* __restrict__ eig, int wt) {
+  quad_wide_block<D, LB, true>(a, eig, wt != 0);
 }
 
 template <typename T, int D, int MASS>
@@ -2044,6 +2093,8 @@ static_assert(QUAD_STATUS_OFF < 128, "the status word lives in the eig block's f
 int g_quad_rows = 1;         // tuning key "quad_rows" (default 1): the fused launch hands the sample rows to row waves through LDS (quad_body: ROWS); 0 = every consumer wave stores its own
 int g_quad_local = 1;        // tuning key "quad_local" (default 1): with "quad_rows" and D <= 3 the records are drawn by producer waves of the consumer's own block (hmc_gauss_quad_local_kernel); 0 = producer blocks behind the consumers', the parity partner
 int g_quad_wide = 1;         // tuning key "quad_wide" (default 1): the local launch hands records and messages over in 16-byte LDS accesses per block of four trajectories (hmc_gauss_quad_wide_kernel); 0 = the 4-byte hand-overs of hmc_gauss_quad_local_kernel, the parity partner
+int g_quad_rows_wt = 1;      // tuning key "quad_rows_wt" (default 1): the row wave of the local and wide launches stores the sample rows write-through at agent scope (quad_rows_body: WT); 0 = plain stores, the parity partner
+int g_quad_lead = 1;         // tuning key "quad_lead" (default 1): the wide launch runs with 512 threads, waves 4-7 drawing records up to the first full pass (hmc_gauss_quad_lead_kernel); 0 = the 256-thread launch, the parity partner
 int g_quad_wide_launches = 0; // debug key "quad_wide_launches": launches of hmc_gauss_quad_wide_kernel since the keys were last reset (the route string does not tell the two local launches apart; tests/test_gpu_quad_wide.py reads it)
 int g_quad_fused = 1;        // tuning key "quad_fused" (default 1): records produced inside the trajectory launch (prepared workspaces only); 0 = a pre-draw launch in front of it
 template <typename T> static bool eig_block_prepared(const GaussArgs<T>& a, int mass_kind);
@@ -2102,17 +2153,25 @@ template <typename T, int D, int MASS> void launch_small(const GaussArgs<T>& a, 
           if (D <= 3 && g_quad_rows && g_quad_local && !g_quad_starve) {
             if constexpr (D <= 3) {
               const int lgrid = (int)((a.C + 15) / 16);                                       // 16 chains per block; the record area of the workspace stays unused
-              if (g_quad_wide) {                                                              // 16-byte hand-overs (quad_body: WIDE)
+              const int wt = g_quad_rows_wt ? 1 : 0;                                          // write-through sample rows (quad_rows_body: WT)
+              if (g_quad_wide && g_quad_lead) {                                               // ... with waves 4-7 drawing in the lead-in (quad_wide_block: LEAD)
                 ++g_quad_wide_launches;
-                if (lbv == 25) hmc_gauss_quad_wide_kernel<D, 25><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
-                else if (lbv == 10) hmc_gauss_quad_wide_kernel<D, 10><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
-                else if (lbv == 5) hmc_gauss_quad_wide_kernel<D, 5><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
-                else hmc_gauss_quad_wide_kernel<D, 0><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+                if (lbv == 25) hmc_gauss_quad_lead_kernel<D, 25><<<lgrid, 512, 0, s>>>(a, a.ws_logu, wt);
+                else if (lbv == 10) hmc_gauss_quad_lead_kernel<D, 10><<<lgrid, 512, 0, s>>>(a, a.ws_logu, wt);
+                else if (lbv == 5) hmc_gauss_quad_lead_kernel<D, 5><<<lgrid, 512, 0, s>>>(a, a.ws_logu, wt);
+                else hmc_gauss_quad_lead_kernel<D, 0><<<lgrid, 512, 0, s>>>(a, a.ws_logu, wt);
               }
-              else if (lbv == 25) hmc_gauss_quad_local_kernel<D, 25><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
-              else if (lbv == 10) hmc_gauss_quad_local_kernel<D, 10><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
-              else if (lbv == 5) hmc_gauss_quad_local_kernel<D, 5><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
-              else hmc_gauss_quad_local_kernel<D, 0><<<lgrid, 256, 0, s>>>(a, a.ws_logu);
+              else if (g_quad_wide) {                                                         // 16-byte hand-overs (quad_body: WIDE)
+                ++g_quad_wide_launches;
+                if (lbv == 25) hmc_gauss_quad_wide_kernel<D, 25><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt);
+                else if (lbv == 10) hmc_gauss_quad_wide_kernel<D, 10><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt);
+                else if (lbv == 5) hmc_gauss_quad_wide_kernel<D, 5><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt);
+                else hmc_gauss_quad_wide_kernel<D, 0><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt);
+              }
+              else if (lbv == 25) hmc_gauss_quad_local_kernel<D, 25><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt);
+              else if (lbv == 10) hmc_gauss_quad_local_kernel<D, 10><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt);
+              else if (lbv == 5) hmc_gauss_quad_local_kernel<D, 5><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt);
+              else hmc_gauss_quad_local_kernel<D, 0><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt);
             }
           }
           else if (g_quad_rows) {

@@ -586,7 +586,13 @@ int hta_jit_rmhmc_implicit_sample(void* module, const HtaCbRmhmcImpArgs* args, i
  * of four trajectories is one 16-byte record read and one 16-byte message write on the integrating wave and one 16-byte read on the
  * row wave - same ring sizes, same groups and barriers, bit-identical results; 0 = the 4-byte hand-overs, the parity partner;
  * the debug key "quad_wide_launches" counts the launches of that kernel since the keys were last reset: the route string is the
- * same for both). */
+ * same for both),
+ * "quad_lead" (1 default = the "quad_wide" launch runs with 512 threads: four more waves draw their share of the records up to and
+ * including the launch's first full pass, the ones the integrating wave waits for with nothing to do, then only walk the groups'
+ * barriers - same records in the same places, bit-identical results; 0 = the 256-thread launch, the parity partner),
+ * "quad_rows_wt" (1 default = the row wave of the "quad_local" / "quad_wide" launches stores the sample rows write-through at agent
+ * scope, so they leave L2 while the launch runs and not in the write-back behind it - same values, same addresses; 0 = plain
+ * stores, the parity partner). */
 int hta_set_tuning(const char* key, int value);
 /* current value of a route key; every key back to its default (test fixtures call this between tests: the keys are
  * process-global).  The environment variable HTA_TUNING_DEFAULTS="key=value,..." moves the DEFAULT of the named keys for the
