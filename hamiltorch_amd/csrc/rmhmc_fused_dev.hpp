@@ -1,5 +1,6 @@
 // Device-side pieces shared by the whole-trajectory RMHMC kernels of the Gaussian-target fast path
-// (rmhmc_fused.hip: one / four / sixteen chains per workgroup, the latter two on the body of rmhmc_rows4_dev.hpp; rmhmc_uv.hip: one or two chains per workgroup on the matrix cores).
+// (rmhmc_fused.hip: one / four / sixteen chains per workgroup, the latter two on the body of rmhmc_rows4_dev.hpp; rmhmc_uv.hip,
+// rmhmc_uvc.hip: one or two chains per workgroup as columns of the matrix instruction, on the shell of rmhmc_cols_dev.hpp).
 #pragma once
 #include <utility>
 #include "common.hpp"
@@ -19,7 +20,7 @@ template <typename T> struct FusedArgs {
 
 typedef float bf4 __attribute__((ext_vector_type(4)));
 
-// ---- the 16-block fp32 matrix instruction with rows x contraction parity inside a wave (rmhmc_uv.hip, rmhmc_uvc.hip)
+// ---- the 16-block fp32 matrix instruction with rows x contraction parity inside a wave (rmhmc_cols_dev.hpp)
 // (XHL = 68, XLD = 140: the 8 operand segments a group of 8 lanes reads at once - 4 columns x 16 bytes, two such groups per
 //  parity - start at banks 0, 12, 24, 36 (+4 for the odd parity): no two share a bank; 64 / 128 would put them on the same four)
 constexpr int XNC = 4, XHL = 68, XLD = 2 * XHL + 4, XWV = 4, XNT = 64 * XWV, XKJ = 52, XQ = XKJ / 4, XSQ = (XQ + 3) / 4;

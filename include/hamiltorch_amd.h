@@ -555,14 +555,8 @@ int hta_jit_rmhmc_implicit_sample(void* module, const HtaCbRmhmcImpArgs* args, i
  * the accept compare, and with the row element and the energy butterfly in one interleaved block; 3 = without that block;
  * 0 = the round-1 instance.  Bit-identical results; 78.5 / 74.1 / 73.25 instructions per trajectory of a lone wave at L = 25:
  * 166.3 -> 157.5 us per 1000 trajectories of BASELINE config 2),
- * "rmhmc_lean" (1 default: rmhmc_uv_kernel without the lane predicate around its LDS stores - both lane halves hold the same
- * values - and without the selects that zero the padding rows, which are exact zeros by
- * construction: the same results bit for bit, ~30 instructions fewer per step of this one-wave-per-SIMD kernel (+1.6 %);
- * 0 = the round-2 instances, the parity partners),
  * "rmhmc_uv_co" (round 4; 1 default = rmhmc_uv_kernel / rmhmc_uvc*_kernel under a 256-register cap, two workgroups per CU: the phase latency of one is
  * filled by the other's matrix instructions; bit-identical to 0; also extends the kernel's range to 4 x CUs chains),
- * "rmhmc_uv_acc" (2 | 4 accumulator chains per product of rmhmc_uv_kernel; 4 needs no s_nop between dependent matrix
- * instructions; another summation order, equal to rounding),
  * "rmhmc_uv_g" (0 = chains per workgroup by chain count; 1 or 2 force it),
  * "rmhmc_uvc" (round 4; 1 default = one-chain workgroups with K == 2 refinements and jitter run on rmhmc_uvc_kernel: one value per
  * lane in the element-wise work and three product phases per step - the second-order term of a solve rides in the idle columns
@@ -600,7 +594,7 @@ int hta_set_tuning(const char* key, int value);
 int hta_get_tuning(const char* key, int* value);
 int hta_reset_tuning(void);
 /* Name (with template arguments) of the dominant kernel the calling thread's last sampling / evaluation call dispatched
- * to, e.g. "hmc_gauss_quad_kernel<3,false,25>", "rmhmc_uv_kernel<1>", "rmhmc_mfma4_kernel<true>", "mlp_mfma_kernel<2,7,0,512>".
+ * to, e.g. "hmc_gauss_quad_kernel<3,false,25>", "rmhmc_uv_kernel<1,co>", "rmhmc_mfma4_kernel<true>", "mlp_mfma_kernel<2,7,0,512>".
  * The string lives in thread-local storage until the next call.  Parity tests and bench.py assert / report the route
  * they exercise with it (the dispatch depends on the chain count and on the process-global tuning keys). */
 const char* hta_last_route(void);

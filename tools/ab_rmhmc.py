@@ -6,7 +6,8 @@ counts and final state (two builds of the library compute the same bits iff the 
     python tools/ab_rmhmc.py 256:- 256:rmhmc_uv_co=1 1024:rmhmc_uv_co=1,rmhmc_uv=2
 
 Environment: HTA_LIB (a developer build of the library, path from the repository root), AB_D, AB_L, AB_T (dimension, steps per
-trajectory, trajectories per call; T defaults by chain count), AB_REPS (timed calls, the best counts).
+trajectory, trajectories per call; T defaults by chain count), AB_JITTER (default 1e-3; 0 = no jitter: K = 0, the route of
+rmhmc_uv_kernel<1,co> at 256 chains), AB_REPS (timed calls, the best counts).
 """
 import hashlib
 import os
@@ -19,13 +20,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import hamiltorch_amd as ht            # noqa: E402
 from hamiltorch_amd import _abi        # noqa: E402
-if os.environ.get("HTA_LIB"):          # a developer build of the library (tools/uv_ablate.sh)
+if os.environ.get("HTA_LIB"):          # a developer build of the library (e.g. the parent commit's, for an A/B of a refactor)
     _abi.LIB_PATH = os.path.join(ROOT, os.environ["HTA_LIB"])
 
 
 def main():
     dev = torch.device("cuda:0")
-    D, L, eps, omega, alpha, jitter = int(os.environ.get("AB_D", "100")), int(os.environ.get("AB_L", "10")), 0.1, 10.0, 1e6, 1e-3
+    D, L, eps, omega, alpha = int(os.environ.get("AB_D", "100")), int(os.environ.get("AB_L", "10")), 0.1, 10.0, 1e6
+    jitter = float(os.environ.get("AB_JITTER", "1e-3")) or None
     g = torch.Generator().manual_seed(0)
     Q = torch.linalg.qr(torch.randn(D, D, generator=g, dtype=torch.float64))[0]
     P = (Q * torch.linspace(0.5, 2.0, D, dtype=torch.float64)) @ Q.T
