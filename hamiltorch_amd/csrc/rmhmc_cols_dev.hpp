@@ -323,7 +323,16 @@ __device__ __forceinline__ void cols_trajectories(const FusedArgs<float>& a, Til
       const T u = u23<T>(philox_block(a.seed, t.chain, n, PURPOSE_MH, 0, 0).x);
       const bool acc = mh_accept<T>(H0u, H1u, lp1u, u);
       const bool reset = (!acc) && ((int)n == a.burn + 1);  // Q2
-      have_next = pre && !reset;
+      // The columns of a group decide TOGETHER whether the next trajectory starts from the hand-over.  The Hamiltonian a chain runs
+      // for itself after its reset holds barriers, LDS exchanges and matrix instructions, and those take their operand rows from all
+      // four columns of a quad - the other chain's and the idle ones too: under one chain's lane mask whatever is computed or
+      // reloaded for an operand inside that branch stays stale in the masked lanes (seen as H_old = -1e8 ... -1e33 after the reset
+      // of one chain of a two-chain group in the 256-register instance of rmhmc_uvc2_kernel, and as an H_old off by 6e-3 in
+      // rmhmc_uv_kernel<2,co>: tests/test_gpu_rmhmc_traj.py).  Every quad holds every column; a dead or idle column has no say.
+      float reset_any = (live && reset) ? 1.f : 0.f;
+      reset_any = fmaxf(reset_any, quad_dpp<0xB1>(reset_any));      // quad_perm [1,0,3,2]
+      reset_any = fmaxf(reset_any, quad_dpp<0x4E>(reset_any));      // quad_perm [2,3,0,1]
+      have_next = pre && reset_any == 0.f;
       {                                                     // H_old, y, z of trajectory t + 1 (the expression of hamiltonian(), same order)
         const T lp0u = of_set_u(lp0), ldv = of_set_v(ld), kinv = of_set_v(kin);
         T Pd1u[NV], Sg1v[NV];

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import hmc_oracle as O
+import rmhmc_traj_cases as RT
 
 pytestmark = pytest.mark.gpu
 MFMA4_DEFAULT = 1      # the library's default for the "rmhmc_mfma4" tuning key (csrc/abi.cpp)
@@ -27,6 +28,13 @@ def dev():
 
 def tt(a, dtype):
     return None if a is None else torch.tensor(np.asarray(a), dtype=dtype, device=dev())
+
+
+def rmhmc_route(D, C, jitter, **keys):
+    """The kernel the launcher sends a float32 run of the fused Gaussian route to under the tuning keys `keys`
+    (tests/rmhmc_traj_cases.py: the launcher's rules restated; the spectrum linspace(.5, 2, D) is cfg3_target's)."""
+    n = torch.cuda.get_device_properties(0).multi_processor_count
+    return RT.expected_route(RT.Case("route", D, C, 0, jitter, 0.0, 0, 0, 0, 0), keys, n)
 
 
 def oracle_momentum(jitter, metric="softabs"):
@@ -737,18 +745,23 @@ def test_wave_momentum_kernel_equals_workgroup_kernel(ht, D, C, jit, batch):
 
 
 @pytest.mark.parametrize("D,C,jit", [(100, 40, 1e-3), (100, 301, 1e-3), (100, 24, None), (37, 30, 5e-2), (7, 9, 1e-3), (64, 18, 2e-3),
-                                     (65, 7, 1e-3), (3, 5, 1e-3), (100, 700, 1e-3)])
+                                     (65, 7, 1e-3), (3, 5, 1e-3), (100, 700, 1e-3), (37, 30, 1.3e-3), (37, 30, 6e-5)])
 def test_uv_kernel_equals_one_chain_kernel(ht, D, C, jit):
-    """rmhmc_uv_kernel (csrc/rmhmc_uv.hip: one chain per workgroup up to 256 chains, two beyond; a chain's state set and its
-    copy are two columns of v_mfma_f32_4x4x1_16b_f32, tracked products) against rmhmc_fused_kernel with every product evaluated
-    ("rmhmc_pair" = 0, one chain per workgroup on the vector ALUs): same streams and update order, sums in a different order ->
-    chain by chain to rounding; an odd chain count (half-empty last workgroup), no jitter (no solve phases), many refinements,
-    D on both sides of a wave's 32 rows, burn-in (Q2 reset), and beyond the default range ("rmhmc_uv" = 2 at 700 chains)."""
+    """The column kernels as "rmhmc_uv" = 2 dispatches them (csrc/rmhmc_uv.hip, rmhmc_uvc.hip: one chain per workgroup up to one per
+    compute unit, two beyond; a chain's state set and its copy are two columns of v_mfma_f32_4x4x1_16b_f32, tracked products) against
+    rmhmc_fused_kernel with every product evaluated ("rmhmc_pair" = 0, one chain per workgroup on the vector ALUs): same streams and
+    update order, sums in a different order -> chain by chain to rounding; an odd chain count (half-empty last workgroup), D on both
+    sides of a wave's 32 rows, burn-in (Q2 reset), and beyond the default range (700 chains).  The route of both runs is asserted.
+    With "rmhmc_uvc" at its default a one-chain group with K = 2 refinements and jitter (jitter 1e-3) runs rmhmc_uvc_kernel and every
+    two-chain group rmhmc_uvc2_kernel; rmhmc_uv_kernel itself takes K = 0 (no jitter: no solve phases), K = 1 (jitter 6e-5) and K = 3
+    (1.3e-3).  Jitter 2e-3 and 5e-2 (series = 0: the log-determinants need a factorisation) are refused by every column kernel:
+    (37, 30, 5e-2) and (64, 18, 2e-3) compare the one-chain kernel's tracked products (K = 7, 3) with its explicit ones, as
+    test_tracked_products_equal_explicit_products does."""
     from hamiltorch_amd import _abi
     T, L, burn = 9, 4, 2
     t, _ = cfg3_target(ht, D, torch.float32, seed=5)
     th0 = tt((0.3 * O.philox_normals(3, np.arange(C), 0, D, O.PURPOSE_INIT, dtype=np.float64)).astype(np.float32), torch.float32)
-    outs = []
+    outs, routes = [], []
     try:
         for uv in (2, 0):
             _abi.set_tuning("rmhmc_uv", uv); _abi.set_tuning("rmhmc_pair", 1 if uv else 0)
@@ -759,12 +772,19 @@ def test_uv_kernel_equals_one_chain_kernel(ht, D, C, jit):
             ws = torch.empty(_abi.rmhmc_workspace_bytes(C, D, 4, T), dtype=torch.uint8, device=dev())
             _abi.rmhmc_gaussian_sample(cur, th0, t.precision, t.mean, t.log_norm, _abi.METRIC_SOFTABS, 1e6, jit, L, 0.1, 10.0,
                                        T, 0, burn, 21, 0, samples, rej, ws, H_old=Ho, H_new=Hn, accept=ac)
+            routes.append(_abi.last_route())
+            assert routes[-1] == rmhmc_route(D, C, jit, rmhmc_uv=uv, rmhmc_pair=1 if uv else 0, rmhmc_mfma4=0, rmhmc_batch=0), routes
             torch.cuda.synchronize()
             outs.append((samples.cpu().numpy(), rej.cpu().numpy(), cur.cpu().numpy(), Ho.cpu().numpy(), Hn.cpu().numpy(), ac.cpu().numpy()))
     finally:
         _abi.set_tuning("rmhmc_uv", 1); _abi.set_tuning("rmhmc_pair", 1)
         _abi.set_tuning("rmhmc_mfma4", MFMA4_DEFAULT); _abi.set_tuning("rmhmc_batch", 1)
     assert np.isfinite(outs[0][0]).all()
+    lean = jit in (None, 6e-5, 1e-3, 1.3e-3)                 # the log-determinant series applies: the column kernels take the run
+    two = C > torch.cuda.get_device_properties(0).multi_processor_count
+    assert routes[0] == ("rmhmc_fused_kernel<float,%d,1,true>" % RT.kh(D) if not lean else "rmhmc_uvc2_kernel<co>" if two else
+                         "rmhmc_uvc_kernel<co>" if jit == 1e-3 else "rmhmc_uv_kernel<1,co>"), routes
+    assert routes[1].startswith("rmhmc_fused_kernel") and routes[1].endswith("false>"), routes
     np.testing.assert_allclose(outs[0][3][0], outs[1][3][0], rtol=2e-5, atol=2e-4)      # H_old / H_new of the first trajectory:
     np.testing.assert_allclose(outs[0][4][0], outs[1][4][0], rtol=2e-5, atol=2e-4)      # before any accept decision
     err = np.abs(outs[0][0] - outs[1][0]).max(axis=(0, 2))
@@ -798,6 +818,9 @@ def test_tracked_products_equal_explicit_products(ht, D, C, jit):
             ws = torch.empty(_abi.rmhmc_workspace_bytes(C, D, 4, T), dtype=torch.uint8, device=dev())
             _abi.rmhmc_gaussian_sample(cur, th0, t.precision, t.mean, t.log_norm, _abi.METRIC_SOFTABS, 1e6, jit, L, 0.1, 10.0,
                                        T, 0, burn, 21, 0, samples, rej, ws, H_old=Ho, H_new=Hn)
+            route = _abi.last_route()                # (one workgroup per CU at most and D = 100: the spill-free instance, "rmhmc_wide")
+            assert route == rmhmc_route(D, C, jit, rmhmc_pair=pair, rmhmc_mfma4=0, rmhmc_batch=0, rmhmc_uv=0), route
+            assert route.startswith("rmhmc_fused_kernel") and route.endswith("true>" if pair else "false>"), route
             torch.cuda.synchronize()
             outs.append((samples.cpu().numpy(), rej.cpu().numpy(), cur.cpu().numpy(), Ho.cpu().numpy(), Hn.cpu().numpy()))
     finally:
