@@ -1296,7 +1296,8 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
       }
       if (DIAG) {
         const bool acc = (accmask >> (threadIdx.x & 63)) & 1;
-        const T ho = 0.5f * quad_sum(eo) - a.log_norm, hn = 0.5f * quad_sum(en) - a.log_norm;
+        // (a dummy lane's eo and en are both the square of its record slot - 2 log u on lane D: they cancel in dH, not in the energies)
+        const T ho = 0.5f * quad_sum(live ? eo : 0.f) - a.log_norm, hn = 0.5f * quad_sum(live ? en : 0.f) - a.log_norm;
         if (k == 0) {
           if (a.H_old) a.H_old[(size_t)t * C + c] = ho;
           if (a.H_new) a.H_new[(size_t)t * C + c] = hn;
@@ -1925,7 +1926,7 @@ __global__ __launch_bounds__(64 * GEN_WAVES) void hmc_gauss_wave_kernel(GaussArg
 // What is left per trajectory are two products with the D x D eigenvector matrix: the rotation of the momentum draw
 // (r = Q^T z: the same Philox normals as the direct kernel) and the sample row q = mu + Q y.  P is diagonalised once per
 // launch by the Jacobi kernel of the RMHMC path (csrc/rmhmc_metric.hip: one workgroup, A and V in LDS; D <= ~140 fp32 /
-// ~99 fp64), then transposed once.  Eig area (workspace): V[D][D] (V[i][k] = component i of eigenvector k) | Vt[D][D] | lam[D].
+// ~99 fp64), in float32 polished (eig_polish_kernel below: one more launch of D blocks, D^3 multiply-adds), then transposed once.  Eig area (workspace): V[D][D] (V[i][k] = component i of eigenvector k) | Vt[D][D] | lam[D].
 // =============================================================================================
 template <typename T>
 __global__ void transpose_kernel(const T* __restrict__ V, T* __restrict__ Vt, int D) {
@@ -1933,6 +1934,35 @@ __global__ void transpose_kernel(const T* __restrict__ V, T* __restrict__ Vt, in
     const int i = e / D, k = e - i * D;
     Vt[k * D + i] = V[e];
   }
+}
+
+// The Jacobi kernel rotates in T: in float32 its ~8 D rotations per column leave every column of V short by the same sign (|v|^2 - 1 =
+// -1e-6 at D = 63 ... 128, off-diagonal V^T V at rounding level), which 0.5 |V^T z|^2 and 0.5 sum lam y^2 carry into H_old and H_new
+// alike (1e-4 at |H| = 100; the difference, and so every decision, does not see it).  One block per column k: v_k <- v_k / |v_k| and
+// lam_k <- v_k^T P v_k / |v_k|^2, sums in double.
+template <typename T>
+__global__ __launch_bounds__(128) void eig_polish_kernel(const T* __restrict__ P, T* __restrict__ V, T* __restrict__ lam, int D) {
+  __shared__ double red[2][128];
+  const int k = blockIdx.x;
+  double nn = 0, rq = 0;
+  for (int i = threadIdx.x; i < D; i += blockDim.x) {
+    const double vi = (double)V[(int64_t)i * D + k];
+    double w = 0;
+    for (int j = 0; j < D; ++j) w += (double)P[(int64_t)i * D + j] * (double)V[(int64_t)j * D + k];
+    nn += vi * vi;
+    rq += vi * w;
+  }
+  red[0][threadIdx.x] = nn; red[1][threadIdx.x] = rq;
+  __syncthreads();
+  for (int h = 64; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) { red[0][threadIdx.x] += red[0][threadIdx.x + h]; red[1][threadIdx.x] += red[1][threadIdx.x + h]; }
+    __syncthreads();
+  }
+  nn = red[0][0]; rq = red[1][0];
+  if (!(nn > 0)) return;                 // (block-uniform: a non-finite or empty column is left as the Jacobi kernel wrote it)
+  const double sc = 1.0 / sqrt(nn);
+  for (int i = threadIdx.x; i < D; i += blockDim.x) V[(int64_t)i * D + k] = (T)((double)V[(int64_t)i * D + k] * sc);
+  if (threadIdx.x == 0) lam[k] = (T)(rq / nn);
 }
 
 template <typename T, int R>
@@ -2260,6 +2290,7 @@ template <typename T, int R> int launch_wave_eig(const GaussArgs<T>& a, hipStrea
   m0.workspace = m0.workspace_bytes ? (char*)V + wave_eig_area_bytes(D, (int)sizeof(T)) : nullptr;
   const int rc = metric_eval<T>(m0, s);
   if (rc) return rc;
+  if constexpr (sizeof(T) == 4) eig_polish_kernel<T><<<D, 128, 0, s>>>(a.P, V, lam, D);      // (float64 rotations leave |v|^2 - 1 at 1e-15: nothing to mend)
   transpose_kernel<T><<<(D * D + 255) / 256, 256, 0, s>>>(V, Vt, D);
   const int grid = (int)((a.C + GEN_WAVES - 1) / GEN_WAVES);
   const size_t lds = (size_t)GEN_WAVES * 64 * R * sizeof(T);
