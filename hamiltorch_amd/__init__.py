@@ -15,3 +15,4 @@ from .samplers import (sample, sample_model, predict_model, sample_split_model, 
 from .util import set_random_seed  # noqa: F401
 from .models import GaussianTarget  # noqa: F401
 from . import samplers  # noqa: F401
+from . import diagnostics  # noqa: F401

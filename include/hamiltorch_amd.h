@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HTA_ABI_VERSION 15
+#define HTA_ABI_VERSION 16
 
 #define HTA_OK 0
 #define HTA_ERR_INVALID (-1)   /* bad argument                           */
@@ -600,6 +600,41 @@ int hta_reset_tuning(void);
 const char* hta_last_route(void);
 /* waits for the recorded event pairs; returns their summed elapsed time and count, then resets. */
 int hta_profile_collect(double* total_ms, int* launches);
+
+/* ---------------------------------------------------------------------------------------------
+ * Convergence diagnostics of samples x[S, C, D] (ABI 16; csrc/diagnostics.hip): bulk effective sample size and split R-hat
+ * of every coordinate, with the definitions of hamiltorch_amd/ess.py - linear autocovariance with divisor S,
+ * acov_t = (1/S) sum_s xc[s] xc[s+t], xc = x - chain mean; mean_var, var_plus (no between-chain term when C == 1); rho_0 = 1;
+ * Geyer's pairs from tau = -1; the floor 1 / log10(S C + 10); ess = S C / tau; R-hat over the first and last S / 2 rows of every chain.
+ *
+ *   x            f32 / f64, unit stride in d; stride_s / stride_c in ELEMENTS (stride_c >= D, stride_s >= (C - 1) stride_c + D), so
+ *                a row offset or a leading slice of coordinates of a sample buffer is read in place.  All arithmetic is fp64.
+ *   workspace    >= hta_diag_workspace_bytes(S, C, D, n_lags) bytes, 8-byte aligned, n_lags = the largest n_lags of the lag /
+ *                finish calls that follow (0 for hta_diag_moments alone).  It carries the per-series means, the walk's state
+ *                (tau, t, done per coordinate) and the partial sums between the calls: one workspace per (x, S, C, D).
+ *   sequence     hta_diag_moments once (writes mean[D], sd[D] = sqrt(var_plus), rhat[D] and resets the walk), then rounds of
+ *                hta_diag_lags (autocovariance sums of the lags [t0, t0 + n_lags), whole blocks of hta_diag_lag_block() lags, at
+ *                most 32 blocks per call, t0 < S) each followed by hta_diag_finish on the same (t0, n_lags): it resumes every
+ *                coordinate's walk over those lags - a coordinate is done when a pair sum is negative, when t + 1 >= S, or when
+ *                var_plus is zero or not finite (tau = ess = NaN) - but not beyond lag_limit (pairs use lags < lag_limit), writes
+ *                tau[D] (floored), ess[D], lags_used[D], done[D] and the number of coordinates not done to *not_done (device
+ *                memory).  The caller reads that one int32 to decide about another round; nothing here synchronises.
+ *   determinism  no floating-point atomics; partial sums are combined in an order fixed by (S, C): equal bits for equal
+ *                input, whatever D, the strides or a split of the coordinates over several calls.
+ * hta_last_route() names the lag kernel ("diag_lags_kernel<float,16>").  hta_diag_segment_rows(): rows of S per grid segment. */
+int hta_diag_lag_block(void);
+int hta_diag_segment_rows(void);
+int64_t hta_diag_workspace_bytes(int64_t S, int64_t C, int64_t D, int n_lags);
+int hta_diag_moments_f32(const float* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, double* mean, double* sd,
+                         double* rhat, void* workspace, int64_t workspace_bytes, void* stream);
+int hta_diag_moments_f64(const double* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, double* mean, double* sd,
+                         double* rhat, void* workspace, int64_t workspace_bytes, void* stream);
+int hta_diag_lags_f32(const float* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, int64_t t0, int n_lags,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int hta_diag_lags_f64(const double* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, int64_t t0, int n_lags,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int hta_diag_finish(int64_t S, int64_t C, int64_t D, int64_t t0, int n_lags, int64_t lag_limit, double* tau, double* ess,
+                    int32_t* lags_used, int32_t* done, int32_t* not_done, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
