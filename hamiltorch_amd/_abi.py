@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhamiltorch_amd.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 MASS_NONE, MASS_DIAG, MASS_FULL = 0, 1, 2
 
@@ -124,6 +124,8 @@ def _sig(scalar):
         "hta_rmhmc_gaussian_prepare": [c_vp, c_vp, c_int, c_f64, c_int, c_f64, c_i64, c_int, c_vp, c_i64, c_vp],
         "hta_diag_moments": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
         "hta_diag_lags": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp],
+        "hta_diag_rank": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+        "hta_diag_rank_folded": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     }
 
 
@@ -136,7 +138,8 @@ PLAIN_SYMBOLS = ["hta_abi_version", "hta_last_error", "hta_device_info", "hta_se
                  "hta_jit_module_info", "hta_jit_hmc_workspace_bytes", "hta_jit_hmc_predraw_bytes", "hta_jit_hmc_sample", "hta_jit_derivs",
                  "hta_jit_rmhmc_workspace_bytes", "hta_jit_rmhmc_sample", "hta_jit_rmhmc_implicit_sample", "hta_jit_split_workspace_bytes", "hta_jit_split_sample",
                  "hta_jit_path_leapfrog", "hta_jit_rolled_sample",
-                 "hta_diag_lag_block", "hta_diag_segment_rows", "hta_diag_workspace_bytes", "hta_diag_finish"]
+                 "hta_diag_lag_block", "hta_diag_segment_rows", "hta_diag_workspace_bytes", "hta_diag_finish",
+                 "hta_diag_rank_tile", "hta_diag_rank_ndtri", "hta_diag_rank_workspace_bytes"]
 TYPED_SYMBOLS = sorted(_sig(c_f32).keys())
 
 
@@ -213,6 +216,11 @@ def load():
         lib.hta_diag_workspace_bytes.argtypes = [c_i64, c_i64, c_i64, c_int]
         lib.hta_diag_workspace_bytes.restype = c_i64
         lib.hta_diag_finish.argtypes = [c_i64, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]
+        lib.hta_diag_rank_tile.argtypes = []
+        lib.hta_diag_rank_ndtri.argtypes = [c_f64]
+        lib.hta_diag_rank_ndtri.restype = c_f64
+        lib.hta_diag_rank_workspace_bytes.argtypes = [c_i64, c_i64, c_i64, c_int]
+        lib.hta_diag_rank_workspace_bytes.restype = c_i64
         for suf, scalar in (("f32", c_f32), ("f64", c_f64)):
             for name, args in _sig(scalar).items():
                 fn = getattr(lib, "%s_%s" % (name, suf))

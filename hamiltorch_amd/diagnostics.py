@@ -15,6 +15,13 @@ The host loop: the first round computes ``LAG_BLOCK`` lags, every later round tw
 round the finish kernel resumes every coordinate's Geyer walk and counts the coordinates still walking into one int32.
 Reading that int32 is the only synchronisation.  Coordinates are processed in chunks sized by ``plan`` so that the
 workspace stays within ``workspace_bytes``; results do not depend on the chunking (nor on strides), bit for bit.
+
+``rank_summary`` adds the rank-normalised half of Vehtari et al. 2021 (csrc/diagnostics_rank.hip): the draws of all chains of a
+coordinate are ranked together by a segmented radix sort on the device, mapped to normal scores, and the scores, the folded
+draws' scores and the 5 % / 95 % indicators go through the same stages:
+
+    r = hamiltorch_amd.diagnostics.rank_summary(out, skip=1)
+    r.ess_bulk, r.ess_tail, r.rhat, r.rhat_bulk, r.rhat_folded, r.q05, r.median, r.q95
 """
 from __future__ import annotations
 
@@ -205,3 +212,179 @@ def ess_min(samples, skip=0, max_lag=None, workspace_bytes=256 << 20):
 def rhat_max(samples, skip=0, workspace_bytes=256 << 20):
     """max over coordinates of split R-hat, NaN coordinates ignored (ess.rhat_max)."""
     return summary(samples, skip, LAG_BLOCK, workspace_bytes).max_rhat()
+
+
+# ---- rank-normalised diagnostics (csrc/diagnostics_rank.hip) -------------------------------------------------------------------------
+#: keys per block and pass of the segmented radix sort (csrc/diagnostics_rank.hip: DIAG_RANK_TILE)
+RANK_TILE = 2048
+
+RankPlan = namedtuple("RankPlan", "chunks n_tiles lags_per_launch bytes_per_coordinate")
+
+
+def _r8(n):
+    return -(-n // 8) * 8
+
+
+def rank_workspace_bytes_for(S, C, D, key_bytes=8):
+    """Bytes of the workspace of hta_diag_rank* for D coordinates (the layout of csrc/diagnostics_rank.hip: diag_rank_layout,
+    restated): keys and uint32 payloads, twice each for the ping-pong of the passes, and 256 digit counts per tile."""
+    N, D, key_bytes = int(S) * int(C), int(D), int(key_bytes)
+    return 2 * _r8(N * D * key_bytes) + 2 * _r8(N * D * 4) + D * -(-N // RANK_TILE) * 1024
+
+
+def rank_bytes_for(S, C, D, n_lags):
+    """Everything rank_summary() holds on the device for D coordinates at a time: the sort's workspace (8-byte keys: the fold's),
+    the derived series z[S, C, D] (fp64; zf reuses it) and I05 / I95 (float), and the workspace of the existing stages."""
+    S, C, D = int(S), int(C), int(D)
+    return rank_workspace_bytes_for(S, C, D, 8) + 16 * S * C * D + workspace_bytes_for(S, C, D, n_lags)
+
+
+def rank_plan(S, C, D, itemsize=4, cap=256 << 20):
+    """plan() for rank_summary(): the coordinate chunks [(d0, d1), ...] under which keys, payloads, their ping-pong buffers, the
+    digit counts, the derived series and the existing stages' workspace together stay within `cap` bytes.  Pure.  (`itemsize` does
+    not enter: the fold sorts 8-byte keys for both sample dtypes.)  ValueError when `cap` cannot hold one coordinate."""
+    S, C, D, cap = int(S), int(C), int(D), int(cap)
+    if S < 1 or C < 1 or D < 1:
+        raise ValueError("diagnostics.rank_plan: bad shape (S=%d C=%d D=%d)" % (S, C, D))
+    if S * C >= 1 << 31:
+        raise ValueError("diagnostics: %d x %d draws per coordinate; the ranking takes fewer than 2^31" % (S, C))
+    n_lags = _lags_per_launch(S)
+    per = rank_bytes_for(S, C, 2, n_lags) // 2
+    dmax = D
+    if rank_bytes_for(S, C, D, n_lags) > cap:
+        dmax = cap // per
+        while dmax > 0 and rank_bytes_for(S, C, dmax, n_lags) > cap:
+            dmax -= 1
+        if dmax < 1:
+            raise ValueError("diagnostics: workspace_bytes=%d cannot hold one coordinate of samples[%d, %d, .] with its ranks (%d bytes)"
+                             % (cap, S, C, rank_bytes_for(S, C, 1, n_lags)))
+    n_tiles = -(-(S * C) // RANK_TILE)
+    dmax = min(dmax, max(1, ((1 << 31) - 1) // n_tiles))                   # (coordinates x tiles is one grid axis)
+    n = -(-D // dmax)
+    size = -(-D // n)
+    return RankPlan([(d0, min(D, d0 + size)) for d0 in range(0, D, size)], n_tiles, n_lags, per)
+
+
+class RankSummary:
+    """Rank-normalised diagnostics of samples[S, C, D] (Vehtari et al. 2021): [D] float64 tensors on the samples' device.
+    `ess_bulk` / `rhat_bulk`: ESS and split R-hat of the rank-normalised draws z; `rhat_folded`: split R-hat of the rank-normalised
+    |x - median|; `rhat` = max(rhat_bulk, rhat_folded); `ess_tail` = min of the ESS of the indicators of the 5 % and 95 % order
+    statistics; `q05`, `median`, `q95`: numpy's linear-interpolation quantiles over all draws.  A coordinate holding a NaN or an
+    infinity is NaN in every field; a constant one is NaN in every ESS and R-hat (its quantiles are the constant).  `route`: the
+    sort kernel the ranking dispatched to."""
+    __slots__ = ("ess_bulk", "ess_tail", "rhat", "rhat_bulk", "rhat_folded", "q05", "median", "q95", "n_draws", "n_chains", "route")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def min_ess(self):
+        """min over coordinates of ess_bulk and ess_tail (NaN if any coordinate has none)."""
+        v = torch.minimum(self.ess_bulk, self.ess_tail)
+        return float("nan") if bool(torch.isnan(v).any()) else float(v.min())
+
+    def max_rhat(self):
+        """max over coordinates of rhat, NaN coordinates ignored."""
+        v = self.rhat[~torch.isnan(self.rhat)]
+        return float(v.max()) if v.numel() else float("nan")
+
+    def to(self, device):
+        return RankSummary(**{k: (getattr(self, k).to(device) if torch.is_tensor(getattr(self, k)) else getattr(self, k)) for k in self.__slots__})
+
+    def __repr__(self):
+        return ("RankSummary(%d draws x %d chains x %d coordinates: min ess %.1f, max rhat %.4f)"
+                % (self.n_draws, self.n_chains, self.rhat.numel(), self.min_ess(), self.max_rhat()))
+
+
+def rank_summary(samples, skip=0, max_lag=None, workspace_bytes=256 << 20):
+    """Rank-normalised diagnostics of `samples`: the inputs, `skip`, `max_lag` and the CPU-in, CPU-out rule of summary().  Per
+    coordinate the S C draws of all chains are ranked together (ties averaged, -0.0 = +0.0) and mapped to normal scores
+    z = Phi^-1((r - 3/8) / (S C + 1/4)); ESS and split R-hat of z, of the folded draws' z and of the tail indicators are those of
+    summary() (the ESS on unsplit chains - ArviZ splits the chains for its ESS first, so its numbers differ slightly).  Returns a
+    RankSummary."""
+    x = _as_samples(samples)
+    skip = int(skip)
+    if skip < 0:
+        raise ValueError("diagnostics: skip=%d" % skip)
+    S, C, D = x.shape[0] - skip, x.shape[1], x.shape[2]
+    if S < 4:
+        raise ValueError("diagnostics: %d draws after skip=%d; at least 4 are needed" % (S, skip))
+    if C < 1 or D < 1:
+        raise ValueError("diagnostics: no chains or no coordinates in samples of shape %s" % (tuple(x.shape),))
+    if max_lag is not None and int(max_lag) < 2:
+        raise ValueError("diagnostics: max_lag=%r; a Geyer pair needs two lags" % (max_lag,))
+    if x.dtype not in (torch.float32, torch.float64):
+        x = x.to(torch.float32)
+    pl = rank_plan(S, C, D, x.element_size(), workspace_bytes)
+    host = not x.is_cuda
+    if host:
+        from .host import _device
+        x = x.to(_device())
+    _abi.require_device(x, "samples")
+    x = x[skip:]
+    if x.stride(2) != 1 or x.stride(1) < D or x.stride(0) < (C - 1) * x.stride(1) + D:
+        x = x.contiguous()
+    out = _run_rank(x, pl, S if max_lag is None else min(S, int(max_lag)))
+    return out.to("cpu") if host else out
+
+
+def _run_rank(x, pl, lag_limit):
+    lib = _abi.load()
+    S, C, D = x.shape
+    dev = x.device
+    suf = _abi._suffix(x)
+    f64 = dict(dtype=torch.float64, device=dev)
+    ess_b, ess_t, rh, rh_b, rh_f, q05, med, q95, centre = (torch.empty(D, **f64) for _ in range(9))
+    bad = torch.empty(D, dtype=torch.int32, device=dev)
+    rank_fn, fold_fn = getattr(lib, "hta_diag_rank_" + suf), getattr(lib, "hta_diag_rank_folded_" + suf)
+    ss, sc, item = x.stride(0), x.stride(1), x.element_size()
+    vp = ctypes.c_void_p
+    route = ""
+    with torch.cuda.device(dev):
+        width = max(d1 - d0 for d0, d1 in pl.chunks)
+        wsb = int(lib.hta_diag_rank_workspace_bytes(S, C, width, 8))
+        ws = _abi.scratch(x, wsb + 16 * S * C * width, "diag_rank")
+        st = _abi._stream(x)
+        for d0, d1 in pl.chunks:
+            k = d1 - d0
+            n = S * C * k
+            z = ws[wsb:wsb + 8 * n].view(torch.float64).view(S, C, k)
+            i05 = ws[wsb + 8 * n:wsb + 12 * n].view(torch.float32).view(S, C, k)
+            i95 = ws[wsb + 12 * n:wsb + 16 * n].view(torch.float32).view(S, C, k)
+            one = Plan([(0, k)], -(-S // SEGMENT_ROWS), min(C, CHAIN_GROUPS), pl.lags_per_launch, 0)
+            xp = vp(x.data_ptr() + d0 * item)
+            at = lambda t: vp(t.data_ptr() + d0 * t.element_size())            # noqa: E731
+            _abi._check(rank_fn(xp, ss, sc, S, C, k, vp(z.data_ptr()), vp(i05.data_ptr()), vp(i95.data_ptr()), at(q05), at(med), at(q95), at(centre),
+                                at(bad), vp(ws.data_ptr()), wsb, st), "hta_diag_rank")
+            route = _abi.last_route()
+            sz = _run(z, one, lag_limit)
+            ess_b[d0:d1], rh_b[d0:d1] = sz.ess_bulk, sz.rhat
+            ess_t[d0:d1] = torch.minimum(_run(i05, one, lag_limit).ess_bulk, _run(i95, one, lag_limit).ess_bulk)
+            _abi._check(fold_fn(xp, ss, sc, S, C, k, at(centre), vp(z.data_ptr()), at(bad), vp(ws.data_ptr()), wsb, st), "hta_diag_rank_folded")
+            rh_f[d0:d1] = _moments_rhat(z)
+    torch.maximum(rh_b, rh_f, out=rh)
+    return RankSummary(ess_bulk=ess_b, ess_tail=ess_t, rhat=rh, rhat_bulk=rh_b, rhat_folded=rh_f, q05=q05, median=med, q95=q95, n_draws=int(S),
+                       n_chains=int(C), route=route)
+
+
+def _moments_rhat(x):
+    """[D] split R-hat of the contiguous series x[S, C, D]: the moments stage alone."""
+    lib = _abi.load()
+    S, C, D = x.shape
+    mean, sd, rhat_ = (torch.empty(D, dtype=torch.float64, device=x.device) for _ in range(3))
+    nbytes = int(lib.hta_diag_workspace_bytes(S, C, D, 0))
+    ws = _abi.scratch(x, nbytes, "diag")
+    vp = ctypes.c_void_p
+    _abi._check(getattr(lib, "hta_diag_moments_" + _abi._suffix(x))(vp(x.data_ptr()), x.stride(0), x.stride(1), S, C, D, vp(mean.data_ptr()), vp(sd.data_ptr()),
+                                                                    vp(rhat_.data_ptr()), vp(ws.data_ptr()), nbytes, _abi._stream(x)), "hta_diag_moments")
+    return rhat_
+
+
+def ess_tail(samples, skip=0, max_lag=None, workspace_bytes=256 << 20):
+    """[D] tail effective sample sizes of samples (see rank_summary)."""
+    return rank_summary(samples, skip, max_lag, workspace_bytes).ess_tail
+
+
+def rhat_rank(samples, skip=0, workspace_bytes=256 << 20):
+    """[D] rank-normalised R-hat of samples: the larger of the bulk and the folded statistic (see rank_summary)."""
+    return rank_summary(samples, skip, LAG_BLOCK, workspace_bytes).rhat

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HTA_ABI_VERSION 16
+#define HTA_ABI_VERSION 17
 
 #define HTA_OK 0
 #define HTA_ERR_INVALID (-1)   /* bad argument                           */
@@ -635,6 +635,37 @@ int hta_diag_lags_f64(const double* x, int64_t stride_s, int64_t stride_c, int64
                       void* workspace, int64_t workspace_bytes, void* stream);
 int hta_diag_finish(int64_t S, int64_t C, int64_t D, int64_t t0, int n_lags, int64_t lag_limit, double* tau, double* ess,
                     int32_t* lags_used, int32_t* done, int32_t* not_done, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Rank-normalisation for the diagnostics above (ABI 17; csrc/diagnostics_rank.hip; Vehtari et al. 2021): per coordinate d of
+ * x[S, C, D] (same x, strides and rules as hta_diag_*), with N = S C < 2^31 draws,
+ *   hta_diag_rank         z[S, C, D] (fp64, contiguous) = Phi^-1((r - 3/8) / (N + 1/4)), r the 1-based rank among the N draws with ties
+ *                         averaged and -0.0 tied with +0.0; i05 / i95[S, C, D] (float: 1 where x <= x_((N-1)/20) resp. x_(19 (N-1)/20),
+ *                         x_(k) the sorted draws, 0-based; else 0); q05 / median / q95[D] = numpy's linear-interpolation quantiles;
+ *                         centre[D] = 0.5 (x_((N-1)/2) + x_(N/2)); bad[D] = the number of NaN / +-inf draws (zeroed by the call).
+ *   hta_diag_rank_folded  zf[S, C, D] = the same z for f = |x - centre[d]| (one fp64 subtract); adds the non-finite f to bad[D].
+ * A coordinate with bad[d] != 0 gets NaN in z, i05, i95, the quantiles and centre.  The derived series are ordinary inputs of
+ * hta_diag_moments / _lags / _finish (z and zf through the _f64 entries, the indicators through the _f32 entries).
+ *   workspace    >= hta_diag_rank_workspace_bytes(S, C, D, key_bytes) bytes, 8-byte aligned: keys and uint32 payloads, twice each,
+ *                and the digit counts.  key_bytes: 4 for hta_diag_rank_f32, 8 for hta_diag_rank_f64 and both folded entries.
+ *   kernels      an LSD radix sort with 8-bit digits, a segment per coordinate, hta_diag_rank_tile() keys per block and pass; each
+ *                pass is three launches (counts, scan, stable scatter) and no workgroup waits for another.  Integer atomics on counts
+ *                only: equal bits for equal input, whatever D, the strides or a split of the coordinates over several calls.
+ * Like every call here they only enqueue work on `stream`.  hta_last_route() names the scatter kernel and its key width
+ * ("diag_rank_scatter_kernel<uint32>").  hta_diag_rank_ndtri(p): the HOST build of the device's Phi^-1 (AS 241 PPND16), for checks. */
+int hta_diag_rank_tile(void);
+double hta_diag_rank_ndtri(double p);
+int64_t hta_diag_rank_workspace_bytes(int64_t S, int64_t C, int64_t D, int key_bytes);
+int hta_diag_rank_f32(const float* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, double* z, float* i05, float* i95,
+                      double* q05, double* median, double* q95, double* centre, int32_t* bad, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+int hta_diag_rank_f64(const double* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, double* z, float* i05, float* i95,
+                      double* q05, double* median, double* q95, double* centre, int32_t* bad, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+int hta_diag_rank_folded_f32(const float* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, const double* centre,
+                             double* zf, int32_t* bad, void* workspace, int64_t workspace_bytes, void* stream);
+int hta_diag_rank_folded_f64(const double* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, const double* centre,
+                             double* zf, int32_t* bad, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
