@@ -34,7 +34,7 @@ int g_rmhmc_momsplit = 1;  // fused RMHMC with jitter: p = chol(P) z1 + sqrt(jit
 int g_gauss_eig = 1;       // small-D identity-mass Gaussian HMC integrates in the eigenbasis of P (0: direct kernel, 2: chain per lane only)
 int g_fill_blocks = 4096;        // grid cap of the pre-draw pass (256-thread blocks, grid-stride)
 int g_quad_max_chains = 65536;   // up to here a chain takes a DPP quad (one eigen-coordinate per lane), beyond a lane
-int g_quad_variant = 7;          // instance of the quad kernel (hmc_gaussian.hip: VAR); 0 = the round-1 instance, 3 = uniform-base addressing + no NaN guard, 7 = + fused row / butterfly block
+int g_quad_variant = 7;          // instance of the quad kernel (hmc_gauss_quad_dev.hpp: VAR); 0 = the round-1 instance, 3 = uniform-base addressing + no NaN guard, 7 = + fused row / butterfly block
 int g_rmhmc_fused = 1;           // 0 = per-evaluation Jacobi path, 3 = fused with two chains per workgroup (parity tests)
 extern int g_metric_mfma, g_metric_general, g_metric_traj, g_metric_second, g_metric_bx3, g_metric_resident, g_metric_select, g_metric_sqrtdraw, g_rmhmc_wide, g_rmhmc_uv_co, g_rmhmc_uv_g, g_rmhmc_uvc, g_quad_fused, g_quad_producers, g_quad_chunks, g_quad_starve, g_quad_rows, g_quad_local, g_quad_wide, g_quad_rows_wt, g_quad_lead, g_quad_wide_launches;         // rmhmc_metric_mfma.hip, rmhmc_fused.hip
 int g_mlp_valu = 0;               // 1 = keep the Bayesian-MLP sampler on the VALU kernel (parity tests of both)

@@ -1,4 +1,5 @@
-// Argument block shared by the fused Gaussian-HMC kernels (hmc_gaussian.hip, hmc_gaussian_quad.hip).
+// Argument block shared by the fused Gaussian-HMC kernels (hmc_gauss_small_dev.hpp, hmc_gauss_quad_dev.hpp, hmc_gauss_wave_dev.hpp)
+// and their dispatcher (hmc_gaussian.hip, the one translation unit that includes the three).
 #pragma once
 #include "common.hpp"
 

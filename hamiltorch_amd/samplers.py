@@ -741,7 +741,7 @@ def adaptation(rho, t, step_size_init, H_t, eps_bar, desired_accept_rate=0.8):
 
 
 class _GaussianHMC(_Engine):
-    """Native path: one persistent-kernel launch runs every trajectory (csrc/hmc_gaussian.hip)."""
+    """Native path: one persistent-kernel launch runs every trajectory (csrc/hmc_gaussian.hip: the dispatcher; the kernels: csrc/hmc_gauss_{small,quad,wave}_dev.hpp)."""
 
     WS_CAP = 128 << 20
 

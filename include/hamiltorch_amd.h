@@ -179,7 +179,7 @@ int hta_hmc_gaussian_prepare_f64(const double* P, int mass_kind, const double* m
                                  void* workspace, int64_t workspace_bytes, void* stream);
 int hta_hmc_gaussian_forget(void* workspace);
 
-/* STATUS WORD of a prepared workspace (ABI 10).  The fused launch of the D <= 4 route (csrc/hmc_gaussian.hip:
+/* STATUS WORD of a prepared workspace (ABI 10).  The fused launch of the D <= 4 route (csrc/hmc_gauss_quad_dev.hpp:
  * hmc_gauss_quad_fused_kernel, the kernel of BASELINE config 2) hands the pre-drawn records from producer blocks to consumer blocks
  * of ONE grid; the consumers' wait is bounded, and a consumer whose bound expires (producers not scheduled: a shared or preempted GPU)
  * ORs 1 into a uint32 word inside the caller's workspace, stops waiting and - when its trajectories are done - overwrites the sample

@@ -149,7 +149,7 @@ ULP32 = 2.0 ** -23
 GUARD = 1e-6               # float64 routes: no decision within GUARD max(1, |H|) of its threshold (tests/mlp_traj_cases.py)
 MAX_OUTSIDE = {"f32": 0.05, "f64": 0.0}
 MASS_KIND = {"none": 0, "diag": 1, "full": 2}
-EIG_ELEMS, QUAD_SLOTS, LDS_BYTES, METRIC_MT = 128, 4, 160 * 1024, 1024          # hmc_gaussian.hip, rmhmc_metric_dev.hpp
+EIG_ELEMS, QUAD_SLOTS, LDS_BYTES, METRIC_MT = 128, 4, 160 * 1024, 1024          # hmc_gauss_small_dev.hpp, hmc_gauss_quad_dev.hpp, rmhmc_metric_dev.hpp
 F_GRID = tuple(round(0.96 - 0.04 * i, 2) for i in range(20)) + tuple(round(0.18 - 0.02 * i, 2) for i in range(7))          # 0.96, 0.92 .. 0.20, 0.18, 0.16 .. 0.06
 SEED_BASE = 21
 

@@ -1,6 +1,6 @@
 """GPU: tuning keys "quad_rows_wt" (the row wave of the local and wide launches stores the sample rows write-through at agent scope)
 and "quad_lead" (the wide launch with 512 threads: waves 4-7 draw records up to the launch's first full pass;
-csrc/hmc_gaussian.hip: hmc_gauss_quad_lead_kernel, quad_local_produce LEAD, quad_rows_body WT).  Neither changes what is computed or
+csrc/hmc_gauss_quad_dev.hpp: hmc_gauss_quad_lead_kernel, quad_local_produce LEAD, quad_rows_body WT).  Neither changes what is computed or
 where it is stored - the same records in the same LDS slots, the same row values at the same addresses - so with both keys on
 (1) the samples, the reject counts and the final state equal, BIT FOR BIT (torch.equal), those with both keys off (0: the
 256-thread launch with plain row stores) and those with "quad_wide" = 0 (the local launch, its rows written through: the other

@@ -1,5 +1,5 @@
 """GPU: tuning key "quad_local" - the fused quad launch whose draw records are made by producer waves of the consumer's own block and
-handed over through LDS (csrc/hmc_gaussian.hip: hmc_gauss_quad_local_kernel) against the launch whose records come from producer
+handed over through LDS (csrc/hmc_gauss_quad_dev.hpp: hmc_gauss_quad_local_kernel) against the launch whose records come from producer
 blocks through memory ("quad_local" = 0), both with row waves ("quad_rows" = 1).  A producer lane runs the cross-block producer's
 arithmetic (quad_make_record) and the groups of trajectories do not change any of it, so samples, reject counts and the final state
 are equal BIT FOR BIT (torch.equal) - over every compiled instance, partial waves and blocks, every shape of the group sequence,

@@ -1,4 +1,4 @@
-"""GPU: tuning key "quad_rows" - the fused quad launch with the sample rows on row waves (csrc/hmc_gaussian.hip: ROWS; the
+"""GPU: tuning key "quad_rows" - the fused quad launch with the sample rows on row waves (csrc/hmc_gauss_quad_dev.hpp: ROWS; the
 integrating wave hands every trajectory's outcome over through an LDS ring) against the same launch with every consumer wave
 storing its own rows ("quad_rows" = 0).  The row wave rebuilds the row element from the accepted eigen-coordinate with the
 instructions the integrating wave used, so samples, reject counts and the final state are equal BIT FOR BIT (torch.equal), over

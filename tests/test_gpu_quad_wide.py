@@ -1,5 +1,5 @@
 """GPU: tuning key "quad_wide" - the local quad launch with 16-byte LDS hand-overs per block of four trajectories
-(csrc/hmc_gaussian.hip: hmc_gauss_quad_wide_kernel, quad_body WIDE) against the local launch with 4-byte hand-overs ("quad_wide" = 0,
+(csrc/hmc_gauss_quad_dev.hpp: hmc_gauss_quad_wide_kernel, quad_body WIDE) against the local launch with 4-byte hand-overs ("quad_wide" = 0,
 hmc_gauss_quad_local_kernel).  Only the rings' addressing and the LDS instructions differ - same records, same arithmetic, same
 groups and barriers - so samples, reject counts and the final state are equal BIT FOR BIT (torch.equal) and the status word is 0.
 Shapes: the smallest at which a block of four positions can go wrong - every compiled instance, half a wave up to three blocks of

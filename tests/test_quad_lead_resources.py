@@ -1,4 +1,4 @@
-"""CPU: the code objects of the wide quad launch with the keys "quad_lead" and "quad_rows_wt" (csrc/hmc_gaussian.hip:
+"""CPU: the code objects of the wide quad launch with the keys "quad_lead" and "quad_rows_wt" (csrc/hmc_gauss_quad_dev.hpp:
 hmc_gauss_quad_lead_kernel<D, LB>, the 512-thread launch, and hmc_gauss_quad_wide_kernel<D, LB>, its 256-thread parity partner) - no
 scratch, 32 KB of LDS at <3, 25>, the registers of the wide instance before the keys existed, and the integrating wave's pass of 32
 trajectories at that instance's instruction count: the keys add lanes that draw and change a store of the row wave, the

@@ -1,4 +1,4 @@
-"""CPU: the code objects of the local quad launch (csrc/hmc_gaussian.hip: hmc_gauss_quad_local_kernel<D, LB>, tuning key "quad_local")
+"""CPU: the code objects of the local quad launch (csrc/hmc_gauss_quad_dev.hpp: hmc_gauss_quad_local_kernel<D, LB>, tuning key "quad_local")
 - no scratch, four waves, the LDS is exactly the message ring plus the record ring, and the integrating wave's hot loop reads its
 records from LDS inside the instruction budget of the cross-block launch (read from the built library)."""
 import os

@@ -1,4 +1,4 @@
-"""CPU: the code objects of the fused quad launch with row waves (csrc/hmc_gaussian.hip: hmc_gauss_quad_fused_kernel<D, LB, NI>,
+"""CPU: the code objects of the fused quad launch with row waves (csrc/hmc_gauss_quad_dev.hpp: hmc_gauss_quad_fused_kernel<D, LB, NI>,
 tuning key "quad_rows") - no scratch, the LDS is exactly the hand-over ring, the registers do not exceed those of the launch
 without row waves, and the integrating wave's hot loop keeps inside its instruction budget (read from the built library)."""
 import os

@@ -1,4 +1,4 @@
-"""CPU: the code objects of the wide quad launch (csrc/hmc_gaussian.hip: hmc_gauss_quad_wide_kernel<D, LB>, tuning key "quad_wide") -
+"""CPU: the code objects of the wide quad launch (csrc/hmc_gauss_quad_dev.hpp: hmc_gauss_quad_wide_kernel<D, LB>, tuning key "quad_wide") -
 no scratch, four waves, the LDS of the local instance, and the integrating wave's hot loop of <3, 25> hands over with 16 LDS
 instructions of 16 bytes per pass, inside the instruction count of the local kernel's hot loop in the same object and inside its
 registers plus the eight record registers (read from the built library and object)."""
