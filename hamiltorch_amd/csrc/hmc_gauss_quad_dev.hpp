@@ -6,6 +6,7 @@
 #include "philox.hpp"
 #include "hmc_gaussian.hpp"
 #include "hmc_gauss_small_dev.hpp"
+#include "quad_prop.hpp"
 
 namespace hta {
 
@@ -123,18 +124,29 @@ template <int NS, int NU, typename F> __device__ __forceinline__ void quad_local
 //
 // The launch FORMS, by name: what quad_body, quad_rows_body and quad_local_produce are instantiated with (D and LB stay ordinary
 // parameters).  Each form is the one above it with one more flag.
-struct QuadFormBase { static constexpr bool DIAG = false, FUSED = false, ROWS = false, LOCAL = false, WIDE = false; static constexpr int VAR = 7; };
+struct QuadFormBase { static constexpr bool DIAG = false, FUSED = false, ROWS = false, LOCAL = false, WIDE = false, PROP = false; static constexpr int VAR = 7; };
 template <bool DIAG_, int VAR_> struct QuadPlain : QuadFormBase { static constexpr bool DIAG = DIAG_; static constexpr int VAR = VAR_; };      // hmc_gauss_quad_kernel: records from a pre-draw launch
 struct QuadFusedForm : QuadFormBase { static constexpr bool FUSED = true; };      // producer blocks behind the consumers' (hmc_gauss_quad_fused_kernel, NI = 0)
 struct QuadRowsForm : QuadFusedForm { static constexpr bool ROWS = true; };       // ... the output side on row waves (NI > 0)
 struct QuadLocalForm : QuadRowsForm { static constexpr bool LOCAL = true; };      // ... the records from producer waves of the block (hmc_gauss_quad_local_kernel)
 struct QuadWideForm : QuadLocalForm { static constexpr bool WIDE = true; };       // ... 16-byte hand-overs (hmc_gauss_quad_wide_kernel, hmc_gauss_quad_lead_kernel)
+// PROP (tuning key "quad_prop", default 1): the twin of any form above whose trajectory applies the half kick, the L steps and the
+// closing half kick as ONE precomputed linear map  y = a yc + b z ; r = c yc + d z  (quad_prop.hpp: the coefficients are the same
+// straight-line arithmetic in float64 on two basis inputs, computed once per launch and lane, in front of the first group) - four
+// instructions instead of 2 L + 2, closer to the float64 trajectory than the float32 chain of steps.  Energies, the butterfly, the
+// compare, the selects, the message, Q2, burn and the NaN rules are the form's own: a coefficient that overflowed makes y or r
+// infinite or NaN, hence dH -inf or NaN, which rejects.  The arithmetic does not depend on the step count at compile time, so a
+// twin has no LB instances: it takes the pass shape of LB = 25 (QUAD_PROP_LB) and a look-ahead of four records in every form.
+template <typename Base> struct QuadPropOf : Base { static constexpr bool PROP = true; };
+constexpr int QUAD_PROP_LB = 25;
 template <int D, int LB, typename Form>
 __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t gt, const QuadFused fz,
                                           uint32_t lds = 0, uint32_t recl = 0) {
   typedef float T;
   constexpr bool DIAG = Form::DIAG, FUSED = Form::FUSED, ROWS = Form::ROWS, LOCAL = Form::LOCAL, WIDE = Form::WIDE;
   constexpr int VAR = Form::VAR;
+  constexpr bool PROP = Form::PROP;
+  static_assert(!PROP || LB == QUAD_PROP_LB, "a propagator twin has one pass shape");
   constexpr bool UADDR = (VAR & 1) != 0, NOGUARD = (VAR & 2) != 0, TAIL = (VAR & 4) != 0;
   static_assert(!Form::ROWS || (Form::FUSED && UADDR && TAIL && !Form::DIAG), "the row-wave form is an instance of the fused launch");
   static_assert(!Form::LOCAL || (Form::ROWS && D < 4), "the local launch is the row-wave form with one record vector");
@@ -190,6 +202,8 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   // a dummy lane integrates nothing: eps = lam = 0, so its y stays 0, its r stays whatever its record slot held (log u or
   // padding) and its energy difference is exactly 0
   const T eps = live ? a.eps : 0.f, nel = -(eps * lam), hl = 0.5f * eps * lam;
+  QuadProp pc{1.f, 0.f, 0.f, 1.f};
+  if constexpr (PROP) pc = quad_prop_coeffs(eps, nel, hl, a.L);      // once per launch, while the first records are on their way
   const size_t C = (size_t)a.C;
   auto bc = [&](T v, int j) {                   // lane j of the quad (j compile-time after unrolling)
     return j == 0 ? quad_bcast<0>(v) : j == 1 ? quad_bcast<1>(v) : j == 2 ? quad_bcast<2>(v) : quad_bcast<3>(v);
@@ -229,7 +243,7 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
   const size_t rec_step = C * W;
   // Records are read NS trajectories ahead: a trajectory (~90 ns at L = 5, ~180 ns at L = 25) is shorter than the ~250 ns
   // an HBM load takes to return, and the look-ahead has to cover it.  The workspace carries QUAD_SLOTS rows of slack.
-  constexpr int NS = quad_fused_ns(LB, FUSED);     // (FUSED: the records come from memory, not from this XCD's L2)
+  constexpr int NS = PROP ? QUAD_FUSED_NS : quad_fused_ns(LB, FUSED);     // (FUSED: the records come from memory, not from this XCD's L2; PROP: a trajectory is a fraction of a load's latency)
   static_assert(NS <= QUAD_SLOTS, "workspace slack");
   constexpr int NZ = WIDE ? 8 : NS;                // (WIDE: the block being consumed and the block being read)
   T zs[NZ], lus[NZ];
@@ -331,27 +345,31 @@ __device__ __forceinline__ void quad_body(const GaussArgs<float>& a, const float
                       : __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, z), (D < 4 ? D : 0) * 0x55,
                                                                             0xF, 0xF, true));
         eo = fmaf(z, z, potc);
-        r = fmaf(-hl, yc, z);
+        if constexpr (PROP) { y = fmaf(pc.b, z, pc.a * yc); r = fmaf(pc.d, z, pc.c * yc); }      // the whole trajectory: S:281-302
+        else r = fmaf(-hl, yc, z);
       }
       // (the empty asm orders the refill after the record's last use, so the load can target the record's own register;
       //  otherwise the scheduler hoists the load and the back-edge copy of its result waits for it)
       if constexpr (ROWS && D < 4) {
       } else if constexpr (UADDR) {
-        asm volatile("" : "+v"(roff[pos]) : "v"(r), "v"(eo), "v"(logu));
+        if constexpr (PROP) asm volatile("" : "+v"(roff[pos]) : "v"(r), "v"(eo), "v"(logu), "v"(y));
+        else asm volatile("" : "+v"(roff[pos]) : "v"(r), "v"(eo), "v"(logu));
         slot = *(grec_t)(recb + roff[pos]);
         if (D == 4) slot_u = *(grec_t)(recb + uoff[pos]);
       } else {
-        asm volatile("" : "+v"(rec) : "v"(r), "v"(eo), "v"(logu));
+        if constexpr (PROP) asm volatile("" : "+v"(rec) : "v"(r), "v"(eo), "v"(logu), "v"(y));
+        else asm volatile("" : "+v"(rec) : "v"(r), "v"(eo), "v"(logu));
         slot = *rec;
         if (D == 4) slot_u = *(rec + ushift);
       }
-      if constexpr (LB > 0) {                                                       // S:283-298
+      if constexpr (PROP) {
+      } else if constexpr (LB > 0) {                                                // S:283-298
 #pragma unroll
         for (int l = 0; l < LB; ++l) { y = fmaf(eps, r, y); r = fmaf(nel, y, r); }
       } else {
         repeat_steps(a.L, [&]() { y = fmaf(eps, r, y); r = fmaf(nel, y, r); });
       }
-      r = fmaf(hl, y, r);                                                           // S:302
+      if constexpr (!PROP) r = fmaf(hl, y, r);                                      // S:302
       // ---- H_new S:995 and the MH test S:1000-1004
       const T pot1 = lam * y * y;
       const T en = fmaf(r, r, pot1);
@@ -671,17 +689,56 @@ __device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const 
       row += C * D;
     }
   };
+  // PROP forms: four trajectories' messages at once, the way of a whole group decided OUTSIDE (STORE: the stored phase; WT):
+  // straight-line code, one exec-mask bracket per four stores.  A propagated trajectory is ~20 instructions on the integrating wave,
+  // and take()'s three branches per trajectory (no row yet? chain past a.C? write-through?) made this wave the slower one
+  // (profiles/r16a_quad_prop.txt).  Same values, same addresses.  The step-by-step forms keep take(): their code is untouched.
+  auto take4 = [&](T m0, T m1, T m2, T m3, auto STORE, auto WT) {
+    const T m[4] = {m0, m1, m2, m3};
+    // to_q of the four, column by column: per element the same v_fmac_f32_dpp sequence on the same operands (the same bits), the
+    // four chains interleaved - the messages come out of LDS, no DPP read follows a VALU write of its source, no wait state is due
+    T qs[4];
+    asm volatile("v_mov_b32 %0, %4\n\tv_mov_b32 %1, %4\n\tv_mov_b32 %2, %4\n\tv_mov_b32 %3, %4"
+                 : "=&v"(qs[0]), "=&v"(qs[1]), "=&v"(qs[2]), "=&v"(qs[3]) : "v"(mu));
+#pragma unroll
+    for (int jc = 0; jc < D; ++jc)
+      asm volatile("v_fmac_f32_dpp %0, %4, %8 quad_perm:[%9,%9,%9,%9] row_mask:0xf bank_mask:0xf\n\t"
+                   "v_fmac_f32_dpp %1, %5, %8 quad_perm:[%9,%9,%9,%9] row_mask:0xf bank_mask:0xf\n\t"
+                   "v_fmac_f32_dpp %2, %6, %8 quad_perm:[%9,%9,%9,%9] row_mask:0xf bank_mask:0xf\n\t"
+                   "v_fmac_f32_dpp %3, %7, %8 quad_perm:[%9,%9,%9,%9] row_mask:0xf bank_mask:0xf"
+                   : "+v"(qs[0]), "+v"(qs[1]), "+v"(qs[2]), "+v"(qs[3])
+                   : "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(Qrow[jc]), "n"(jc));
+    T v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool acc = __builtin_bit_cast(uint32_t, m[j]) != QUAD_ROWS_REJECT;
+      const T q = qs[j];
+      qc = acc ? q : qc;
+      v[j] = qc;
+      accepted += acc ? 1 : 0;
+    }
+    if constexpr (decltype(STORE)::value) {
+      if (on) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if constexpr (decltype(WT)::value) __hip_atomic_store(row + el + (size_t)j * C * D, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          else row[el + (size_t)j * C * D] = v[j];
+        }
+      }
+      row += 4 * C * D;
+    }
+  };
   auto group = [&](auto G, bool q2) {
     asm volatile("s_barrier" ::: "memory");      // the integrator has filled this buffer
     constexpr int g = decltype(G)::value;
-    if constexpr (WIDE && g % 4 == 0) {           // one 16-byte read per block of four positions (quad_body: WIDE)
+    if constexpr (!Form::PROP && WIDE && g % 4 == 0) {           // one 16-byte read per block of four positions (quad_body: WIDE)
       for (int i = 0; i < g; i += 4) {
         typedef float V4f __attribute__((ext_vector_type(4)));
         V4f m;
         asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(m) : "v"(lds + (uint32_t)i * 256u) : "memory");
         take(m[0], false); take(m[1], false); take(m[2], false); take(m[3], false);
       }
-    } else if constexpr (g % 4 == 0) {
+    } else if constexpr (!Form::PROP && g % 4 == 0) {
       for (int i = 0; i < g; i += 4) {
         T m0, m1, m2, m3;
         asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:256\n\tds_read_b32 %2, %4 offset:512\n\tds_read_b32 %3, %4 offset:768\n\t"
@@ -689,6 +746,29 @@ __device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const 
                      : "=&v"(m0), "=&v"(m1), "=&v"(m2), "=&v"(m3) : "v"(lds + (uint32_t)i * 256u) : "memory");
         take(m0, false); take(m1, false); take(m2, false); take(m3, false);
       }
+    } else if constexpr (g % 4 == 0) {                            // PROP: the blocks below
+      auto blocks = [&](auto STORE, auto WT) {
+        typedef float V4f __attribute__((ext_vector_type(4)));
+        typedef const __attribute__((address_space(3))) V4f* lvec_t;
+        V4f mw = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (WIDE) mw = *(lvec_t)(uintptr_t)lds;      // (typed LDS reads: the compiler keeps their wait counts; the barrier's clobber keeps them behind it)
+        for (int i = 0; i < g; i += 4) {
+          if constexpr (WIDE) {                   // one 16-byte read per block of four positions (quad_body: WIDE), the next block's
+            const V4f m = mw;                     // issued before this block's work: its LDS round trip hides behind four trajectories
+            if (i + 4 < g) mw = *(lvec_t)(uintptr_t)(lds + (uint32_t)(i + 4) * 256u);
+            take4(m[0], m[1], m[2], m[3], STORE, WT);
+          } else {
+            T m0, m1, m2, m3;
+            asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:256\n\tds_read_b32 %2, %4 offset:512\n\tds_read_b32 %3, %4 offset:768\n\t"
+                         "s_waitcnt lgkmcnt(0)"
+                         : "=&v"(m0), "=&v"(m1), "=&v"(m2), "=&v"(m3) : "v"(lds + (uint32_t)i * 256u) : "memory");
+            take4(m0, m1, m2, m3, STORE, WT);
+          }
+        }
+      };
+      if (!row) blocks(std::false_type{}, std::false_type{});
+      else if (wt) blocks(std::true_type{}, std::true_type{});
+      else blocks(std::true_type{}, std::false_type{});
     } else {
       for (int i = 0; i < g; ++i) {
         T m;
@@ -735,6 +815,11 @@ __device__ __forceinline__ void quad_rows_body(const GaussArgs<float>& a, const 
 template <int D, bool DIAG, int LB, int VAR = 0>
 __global__ __launch_bounds__(64) void hmc_gauss_quad_kernel(GaussArgs<float> a, const float* __restrict__ eig) {
   quad_body<D, LB, QuadPlain<DIAG, VAR>>(a, eig, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, QuadFused{nullptr, 1, 0u, 0, nullptr, 0});
+}
+// its propagator twin (quad_body: PROP): any L, the DIAG instance included
+template <int D, bool DIAG, int VAR = 0>
+__global__ __launch_bounds__(64) void hmc_gauss_quad_prop_kernel(GaussArgs<float> a, const float* __restrict__ eig) {
+  quad_body<D, QUAD_PROP_LB, QuadPropOf<QuadPlain<DIAG, VAR>>>(a, eig, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, QuadFused{nullptr, 1, 0u, 0, nullptr, 0});
 }
 
 // one record (csrc: rng_fill_small_kernel's body): the draws of trajectory n of global chain `chain`, rotated into the eigenbasis, and
@@ -792,10 +877,11 @@ constexpr int QUAD_FUSED_NT = 256;         // four waves per block: a producer b
 constexpr int QUAD_ROWS_NI = 2;            // with two pairs per block the integrating waves and the row waves sit on different SIMDs of the
                                            // CU (waves of a workgroup are dealt out round robin) and the block size is the producers' own
 constexpr int quad_fused_threads(int NI) { return NI > 0 ? 128 * NI : QUAD_FUSED_NT; }
-template <int D, int LB, int NI = 0>
-__global__ __launch_bounds__(quad_fused_threads(NI)) void hmc_gauss_quad_fused_kernel(GaussArgs<float> a, const float* __restrict__ eig, QuadFused fz,
-                                                                                      int nc, int spc, uint32_t* done) {
+template <int D, int LB, int NI, bool PROP>
+__device__ __forceinline__ void quad_fused_block(const GaussArgs<float>& a, const float* __restrict__ eig, const QuadFused& fz, int nc, int spc, uint32_t* done) {
   constexpr int NT = quad_fused_threads(NI);
+  typedef std::conditional_t<PROP, QuadPropOf<QuadRowsForm>, QuadRowsForm> RowsForm;
+  typedef std::conditional_t<PROP, QuadPropOf<QuadFusedForm>, QuadFusedForm> FusedForm;
   if ((int)blockIdx.x >= nc) {
     // producer block b of spc: its slices of every chunk, chunk by chunk; one count per block and chunk
     const int b = (int)blockIdx.x - nc;
@@ -818,12 +904,12 @@ __global__ __launch_bounds__(quad_fused_threads(NI)) void hmc_gauss_quad_fused_k
     const int wave = (int)(threadIdx.x >> 6), pair = wave < NI ? wave : wave - NI;
     const uint32_t lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)ring + (uint32_t)(pair * 2 * NU * 256) + (uint32_t)(threadIdx.x & 63) * 4u;
     const int64_t gt = ((int64_t)blockIdx.x * NI + pair) * 64 + (threadIdx.x & 63);
-    if (wave >= NI) { quad_rows_body<D, LB, QuadRowsForm>(a, eig, gt, lds); return; }
+    if (wave >= NI) { quad_rows_body<D, LB, RowsForm>(a, eig, gt, lds); return; }
     __builtin_amdgcn_s_setprio(3);
-    quad_body<D, LB, QuadRowsForm>(a, eig, gt, fz, lds);
+    quad_body<D, LB, RowsForm>(a, eig, gt, fz, lds);
   } else {
     __builtin_amdgcn_s_setprio(3);                 // a consumer's time is its issue rate: it goes first where a producer shares its SIMD
-    quad_body<D, LB, QuadFusedForm>(a, eig, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, fz);
+    quad_body<D, LB, FusedForm>(a, eig, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, fz);
   }
   if (threadIdx.x == 0) {
     const uint32_t old = __hip_atomic_fetch_add(done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
@@ -832,6 +918,17 @@ __global__ __launch_bounds__(quad_fused_threads(NI)) void hmc_gauss_quad_fused_k
       __hip_atomic_store(done, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+}
+template <int D, int LB, int NI = 0>
+__global__ __launch_bounds__(quad_fused_threads(NI)) void hmc_gauss_quad_fused_kernel(GaussArgs<float> a, const float* __restrict__ eig, QuadFused fz,
+                                                                                      int nc, int spc, uint32_t* done) {
+  quad_fused_block<D, LB, NI, false>(a, eig, fz, nc, spc, done);
+}
+// its propagator twin (quad_body: PROP): the same producers, counters and rings
+template <int D, int NI = 0>
+__global__ __launch_bounds__(quad_fused_threads(NI)) void hmc_gauss_quad_fused_prop_kernel(GaussArgs<float> a, const float* __restrict__ eig, QuadFused fz,
+                                                                                           int nc, int spc, uint32_t* done) {
+  quad_fused_block<D, QUAD_PROP_LB, NI, true>(a, eig, fz, nc, spc, done);
 }
 
 
@@ -859,7 +956,10 @@ __global__ __launch_bounds__(quad_fused_threads(NI)) void hmc_gauss_quad_fused_k
 // a.C or not, a launch shorter than one group or not - executes one "s_waitcnt lgkmcnt(0) ; s_barrier" per group of
 // quad_local_groups, in that order, and the two closing barriers: the barrier sequence of every role is a function of the launch
 // arguments alone, whatever the sweeps are.
-template <int D, int LB, typename Form>
+// CPB (the propagator's 512-thread twin, quad_wide_block): the chains of a block, 16, 8 or 4.  A block's lanes of chain slots >= CPB
+// are switched off like lanes past a.C, nobody draws for them, and a producer lane's share becomes (position l / CPB, chain l % CPB):
+// with four chains 128 lanes cover the 32 positions of a pass in ONE sweep.
+template <int D, int LB, typename Form, int CPB = 16>
 __device__ __forceinline__ void quad_local_produce(const GaussArgs<float>& a, const float* __restrict__ eig, const int64_t c0, const uint32_t recl,
                                                    const int pl, const int nl, const int pl_lead, const int nl_lead) {
   constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
@@ -869,15 +969,17 @@ __device__ __forceinline__ void quad_local_produce(const GaussArgs<float>& a, co
   typedef __attribute__((address_space(3))) V4f* lvec_t;
   typedef __attribute__((address_space(3))) float* lflt_t;
   (void)(lvec_t)nullptr;
-  const int chain = pl_lead & 15;
+  static_assert(CPB == 16 || CPB == 8 || CPB == 4, "a power of two of chain slots; sweeps of 64 k lanes stay whole blocks of four positions");
+  constexpr int CS = CPB == 16 ? 4 : (CPB == 8 ? 3 : 2);                       // log2 CPB
+  const int chain = pl_lead & (CPB - 1);
   const int64_t c = min(c0 + chain, a.C - 1);                                   // (past a.C: the last chain again, as the integrator does)
   const uint64_t gchain = a.chain_offset + (uint64_t)c;
   uint32_t buf = recl;                                                          // the record buffer being filled
   const uint32_t buf_both = 2u * recl + (uint32_t)(NU * 256);
   bool lead = true;
   quad_local_groups<NS, NU>(a, [&](int t0, int, auto G, auto) {
-    const int l = lead ? pl_lead : pl, step = (lead ? nl_lead : nl) >> 4;       // (step: a multiple of four positions - whole blocks of WIDE)
-    const int p0 = l >= 0 ? l >> 4 : NU;                                        // (NU: past every group)
+    const int l = lead ? pl_lead : pl, step = (lead ? nl_lead : nl) >> CS;      // (step: a multiple of four positions - whole blocks of WIDE)
+    const int p0 = l >= 0 ? l >> CS : NU;                                       // (NU: past every group)
     const uint32_t dst = buf + (WIDE ? (uint32_t)((p0 >> 2) * 1024 + chain * 64 + (p0 & 3) * 4) : (uint32_t)(p0 * 256 + chain * 16));
     for (int p = p0; p < decltype(G)::value; p += step) {                       // (p < NU: inside the buffer)
       float rec[4];
@@ -895,8 +997,9 @@ __device__ __forceinline__ void quad_local_produce(const GaussArgs<float>& a, co
   });
   asm volatile("s_barrier\n\ts_barrier" ::: "memory");                          // the last group's hand-over and the status message: the other roles'
 }
-template <int D, int LB>
-__global__ __launch_bounds__(256) void hmc_gauss_quad_local_kernel(GaussArgs<float> a, const float* __restrict__ eig, int wt) {
+template <int D, int LB, bool PROP>
+__device__ __forceinline__ void quad_local_block(const GaussArgs<float>& a, const float* __restrict__ eig, int wt) {
+  typedef std::conditional_t<PROP, QuadPropOf<QuadLocalForm>, QuadLocalForm> Form;
   constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
   __shared__ __attribute__((aligned(16))) float ring[2 * NU * 64 + 2 * NU * 64];      // messages (64 lanes x 4 bytes) | records (16 chains x 16 bytes), two passes each
   const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
@@ -904,10 +1007,18 @@ __global__ __launch_bounds__(256) void hmc_gauss_quad_local_kernel(GaussArgs<flo
   const int64_t gt = (int64_t)blockIdx.x * 64 + lane;
   if (wave == 0) {
     __builtin_amdgcn_s_setprio(3);
-    quad_body<D, LB, QuadLocalForm>(a, eig, gt, QuadFused{nullptr, 1, 0u, 0, nullptr, 0}, msgs + (uint32_t)lane * 4u, recs + (uint32_t)lane * 4u);
+    quad_body<D, LB, Form>(a, eig, gt, QuadFused{nullptr, 1, 0u, 0, nullptr, 0}, msgs + (uint32_t)lane * 4u, recs + (uint32_t)lane * 4u);
   }
-  else if (wave == 1) quad_rows_body<D, LB, QuadLocalForm>(a, eig, gt, msgs + (uint32_t)lane * 4u, wt != 0);
-  else quad_local_produce<D, LB, QuadLocalForm>(a, eig, (int64_t)blockIdx.x * 16, recs, (int)threadIdx.x - 128, 128, (int)threadIdx.x - 128, 128);
+  else if (wave == 1) quad_rows_body<D, LB, Form>(a, eig, gt, msgs + (uint32_t)lane * 4u, wt != 0);
+  else quad_local_produce<D, LB, Form>(a, eig, (int64_t)blockIdx.x * 16, recs, (int)threadIdx.x - 128, 128, (int)threadIdx.x - 128, 128);
+}
+template <int D, int LB>
+__global__ __launch_bounds__(256) void hmc_gauss_quad_local_kernel(GaussArgs<float> a, const float* __restrict__ eig, int wt) {
+  quad_local_block<D, LB, false>(a, eig, wt);
+}
+template <int D>
+__global__ __launch_bounds__(256) void hmc_gauss_quad_local_prop_kernel(GaussArgs<float> a, const float* __restrict__ eig, int wt) {
+  quad_local_block<D, QUAD_PROP_LB, true>(a, eig, wt);
 }
 // WIDE (tuning key "quad_wide"): the local launch - the same roles, rings of the same sizes, the same groups and barriers - with
 // 16-byte hand-overs per block of four positions (quad_body: WIDE); a lane's base in a block of either ring is lane x 16 bytes.
@@ -919,24 +1030,46 @@ __global__ __launch_bounds__(256) void hmc_gauss_quad_local_kernel(GaussArgs<flo
 // idle roles) first in the sweep, so the pass is two wave-sweeps on each SIMD instead of four on two.  Behind it they draw
 // nothing and walk the groups to the end with everybody's barriers; they never leave early.  Same records in the same places:
 // results are bit-identical to the 256-thread launch (tests/test_gpu_quad_lead.py).
-template <int D, int LB, bool LEAD>
-__device__ __forceinline__ void quad_wide_block(const GaussArgs<float>& a, const float* __restrict__ eig, const bool wt) {
+// PROP twins (hmc_gauss_quad_wide_prop_kernel, hmc_gauss_quad_lead_prop_kernel).  A propagated trajectory is ~20 instructions on
+// the integrating wave, a record ~290 on a producer lane: the two producer waves of the step-by-step launch (eight positions of
+// 16 chains per sweep) no longer keep up, and 64 blocks leave three quarters of the chip without a record to draw.  The 512-thread
+// twin therefore runs with CPB = 4 chains per block up to 1024 chains (tuning key "quad_prop_chains"; quad_local_produce: CPB):
+// waves 2-3 cover a pass of 32 positions in one sweep, on SIMDs that hold neither the integrating wave nor the row wave.  Measured
+// (profiles/r16a_quad_prop.txt): producers that draw nothing are not faster - the integrating wave's issue binds.
+// SWEEP (tuning key "quad_prop_sweep", default 0, the 512-thread twin only) names the waves that draw
+// BEHIND the first full pass: 0 = waves 2-3 as before, 1 = waves 2, 3, 6, 7 (256 lanes, 16 positions per sweep: two drawing waves
+// on each of the two SIMDs that hold neither the integrating wave nor the row wave), 2 = waves 2-7 (384 lanes, the lead-in's
+// sweep).  Which lanes draw is all a sweep decides (quad_local_produce: INVARIANT): every wave walks every group and barrier.
+template <int D, int LB, bool LEAD, bool PROP = false, int CPB = 16>
+__device__ __forceinline__ void quad_wide_block(const GaussArgs<float>& a, const float* __restrict__ eig, const bool wt, const int sweep = 0) {
+  typedef std::conditional_t<PROP, QuadPropOf<QuadWideForm>, QuadWideForm> Form;
   constexpr int NS = quad_fused_ns(LB, true), NU = quad_nu(LB, NS, true);
   static_assert(NS == 4 && NU % 4 == 0, "groups are whole blocks of four positions, or single ones");
   __shared__ __attribute__((aligned(16))) float ring[2 * NU * 64 + 2 * NU * 64];      // as the local launch's: messages | records, two passes each
   const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
   const uint32_t msgs = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)ring, recs = msgs + (uint32_t)(2 * NU * 256);
-  const int64_t gt = (int64_t)blockIdx.x * 64 + lane;
+  const int64_t gt = CPB == 16 || lane < 4 * CPB ? (int64_t)blockIdx.x * (4 * CPB) + lane : a.C * 4;      // (a chain slot >= CPB: off, like a chain past a.C)
   if (wave == 0) {
     __builtin_amdgcn_s_setprio(3);
-    quad_body<D, LB, QuadWideForm>(a, eig, gt, QuadFused{nullptr, 1, 0u, 0, nullptr, 0}, msgs + (uint32_t)lane * 16u, recs + (uint32_t)lane * 16u);
+    quad_body<D, LB, Form>(a, eig, gt, QuadFused{nullptr, 1, 0u, 0, nullptr, 0}, msgs + (uint32_t)lane * 16u, recs + (uint32_t)lane * 16u);
   }
-  else if (wave == 1) quad_rows_body<D, LB, QuadWideForm>(a, eig, gt, msgs + (uint32_t)lane * 16u, wt);
+  else if (wave == 1) quad_rows_body<D, LB, Form>(a, eig, gt, msgs + (uint32_t)lane * 16u, wt);
   else if constexpr (LEAD) {
     const int lw = wave < 4 ? wave : (wave < 6 ? wave - 4 : wave - 2);               // place in the lead sweep: waves 4 5 2 3 6 7
-    quad_local_produce<D, LB, QuadWideForm>(a, eig, (int64_t)blockIdx.x * 16, recs, wave < 4 ? (int)threadIdx.x - 128 : -1, 128, lw * 64 + lane, 384);
+    int pl = wave < 4 ? (int)threadIdx.x - 128 : -1, nl = 128;                         // the sweep behind the first full pass
+    if (PROP && sweep == 1) { pl = wave < 4 ? (int)threadIdx.x - 128 : (wave >= 6 ? (int)threadIdx.x - 256 : -1); nl = 256; }
+    if (PROP && sweep == 2) { pl = lw * 64 + lane; nl = 384; }
+    quad_local_produce<D, LB, Form, CPB>(a, eig, (int64_t)blockIdx.x * CPB, recs, pl, nl, lw * 64 + lane, 384);
   }
-  else quad_local_produce<D, LB, QuadWideForm>(a, eig, (int64_t)blockIdx.x * 16, recs, (int)threadIdx.x - 128, 128, (int)threadIdx.x - 128, 128);
+  else quad_local_produce<D, LB, Form, CPB>(a, eig, (int64_t)blockIdx.x * CPB, recs, (int)threadIdx.x - 128, 128, (int)threadIdx.x - 128, 128);
+}
+template <int D>
+__global__ __launch_bounds__(256) void hmc_gauss_quad_wide_prop_kernel(GaussArgs<float> a, const float* __restrict__ eig, int wt) {
+  quad_wide_block<D, QUAD_PROP_LB, false, true>(a, eig, wt != 0);
+}
+template <int D, int CPB>
+__global__ __launch_bounds__(512) void hmc_gauss_quad_lead_prop_kernel(GaussArgs<float> a, const float* __restrict__ eig, int wt, int sweep) {
+  quad_wide_block<D, QUAD_PROP_LB, true, true, CPB>(a, eig, wt != 0, sweep);
 }
 template <int D, int LB>
 __global__ __launch_bounds__(256) void hmc_gauss_quad_wide_kernel(GaussArgs<float> a, const float* __restrict__ eig, int wt) {

@@ -49,6 +49,9 @@ int g_quad_wide = 1;         // tuning key "quad_wide" (default 1): the local la
 int g_quad_rows_wt = 1;      // tuning key "quad_rows_wt" (default 1): the row wave of the local and wide launches stores the sample rows write-through at agent scope (quad_rows_body: WT); 0 = plain stores, the parity partner
 int g_quad_lead = 1;         // tuning key "quad_lead" (default 1): the wide launch runs with 512 threads, waves 4-7 drawing records up to the first full pass (hmc_gauss_quad_lead_kernel); 0 = the 256-thread launch, the parity partner
 int g_quad_wide_launches = 0; // debug key "quad_wide_launches": launches of hmc_gauss_quad_wide_kernel since the keys were last reset (the route string does not tell the two local launches apart; tests/test_gpu_quad_wide.py reads it)
+int g_quad_prop = 1;         // tuning key "quad_prop" (default 1): every quad launch form applies a trajectory's L steps as one precomputed linear map (quad_body: PROP, the ..._prop_kernel twins); 0 = the step-by-step instances, the parity partner
+int g_quad_prop_sweep = 0;   // tuning key "quad_prop_sweep" (default 0): the waves of hmc_gauss_quad_lead_prop_kernel that draw behind the first full pass (quad_wide_block: SWEEP) - 0 = waves 2-3, 1 = waves 2, 3, 6, 7, 2 = waves 2-7
+int g_quad_prop_chains = 0;  // tuning key "quad_prop_chains" (default 0): chains per block of hmc_gauss_quad_lead_prop_kernel (quad_local_produce: CPB), 16, 8 or 4; 0 = the fewest that keep the launch within 256 blocks (4 up to 1024 chains, 8 up to 2048, 16 beyond)
 int g_quad_fused = 1;        // tuning key "quad_fused" (default 1): records produced inside the trajectory launch (prepared workspaces only); 0 = a pre-draw launch in front of it
 template <typename T> static bool eig_block_prepared(const GaussArgs<T>& a, int mass_kind);
 template <typename T> static bool quad_route(const GaussArgs<T>& a);
@@ -119,7 +122,19 @@ template <int D> static void launch_quad(const GaussArgs<float>& a, int mass_kin
       if constexpr (D <= 3) {
         const int lgrid = (int)((a.C + 15) / 16);                                       // 16 chains per block; the record area of the workspace stays unused
         const int wt = g_quad_rows_wt ? 1 : 0;                                          // write-through sample rows (quad_rows_body: WT)
-        if (g_quad_wide && g_quad_lead) {                                               // ... with waves 4-7 drawing in the lead-in (quad_wide_block: LEAD)
+        if (g_quad_prop) {                                                              // the same three launches, the trajectory as one linear map (quad_body: PROP)
+          if (g_quad_wide) ++g_quad_wide_launches;
+          const int sweep = g_quad_prop_sweep < 0 ? 0 : (g_quad_prop_sweep > 2 ? 2 : g_quad_prop_sweep);
+          const int cpb = g_quad_prop_chains == 16 || g_quad_prop_chains == 8 || g_quad_prop_chains == 4 ? g_quad_prop_chains
+                                                                                                           : (a.C <= 1024 ? 4 : (a.C <= 2048 ? 8 : 16));
+          const int pgrid = (int)((a.C + cpb - 1) / cpb);
+          if (g_quad_wide && g_quad_lead && cpb == 4) hmc_gauss_quad_lead_prop_kernel<D, 4><<<pgrid, 512, 0, s>>>(a, a.ws_logu, wt, sweep);
+          else if (g_quad_wide && g_quad_lead && cpb == 8) hmc_gauss_quad_lead_prop_kernel<D, 8><<<pgrid, 512, 0, s>>>(a, a.ws_logu, wt, sweep);
+          else if (g_quad_wide && g_quad_lead) hmc_gauss_quad_lead_prop_kernel<D, 16><<<pgrid, 512, 0, s>>>(a, a.ws_logu, wt, sweep);
+          else if (g_quad_wide) hmc_gauss_quad_wide_prop_kernel<D><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt);
+          else hmc_gauss_quad_local_prop_kernel<D><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt);
+        }
+        else if (g_quad_wide && g_quad_lead) {                                          // ... with waves 4-7 drawing in the lead-in (quad_wide_block: LEAD)
           ++g_quad_wide_launches;
           with_lb(lbv, [&](auto LB) { hmc_gauss_quad_lead_kernel<D, decltype(LB)::value><<<lgrid, 512, 0, s>>>(a, a.ws_logu, wt); });
         }
@@ -130,6 +145,10 @@ template <int D> static void launch_quad(const GaussArgs<float>& a, int mass_kin
         else with_lb(lbv, [&](auto LB) { hmc_gauss_quad_local_kernel<D, decltype(LB)::value><<<lgrid, 256, 0, s>>>(a, a.ws_logu, wt); });
       }
     }
+    else if (g_quad_prop) {
+      if (g_quad_rows) hmc_gauss_quad_fused_prop_kernel<D, NI><<<fgrid, quad_fused_threads(NI), 0, s>>>(a, a.ws_logu, fz, cgrid, spc, done);
+      else hmc_gauss_quad_fused_prop_kernel<D><<<fgrid, QUAD_FUSED_NT, 0, s>>>(a, a.ws_logu, fz, cgrid, spc, done);
+    }
     else if (g_quad_rows)
       with_lb(lbv, [&](auto LB) { hmc_gauss_quad_fused_kernel<D, decltype(LB)::value, NI><<<fgrid, quad_fused_threads(NI), 0, s>>>(a, a.ws_logu, fz, cgrid, spc, done); });
     else
@@ -138,9 +157,13 @@ template <int D> static void launch_quad(const GaussArgs<float>& a, int mass_kin
   else if (!diag && (g_quad_variant == 3 || g_quad_variant == 7) && a.C <= (1 << 20)) {
     // "quad_variant": 3 = uniform bases + 32-bit lane offsets, no NaN guard; 7 = also the fused row / butterfly block
     note_route("hmc_gauss_quad_kernel<%d,false,%d,%d>", D, lbv, g_quad_variant);
-    if (g_quad_variant == 3) with_lb(lbv, [&](auto LB) { hmc_gauss_quad_kernel<D, false, decltype(LB)::value, 3><<<qgrid, 64, 0, s>>>(a, a.ws_logu); });
+    if (g_quad_prop && g_quad_variant == 3) hmc_gauss_quad_prop_kernel<D, false, 3><<<qgrid, 64, 0, s>>>(a, a.ws_logu);
+    else if (g_quad_prop) hmc_gauss_quad_prop_kernel<D, false, 7><<<qgrid, 64, 0, s>>>(a, a.ws_logu);
+    else if (g_quad_variant == 3) with_lb(lbv, [&](auto LB) { hmc_gauss_quad_kernel<D, false, decltype(LB)::value, 3><<<qgrid, 64, 0, s>>>(a, a.ws_logu); });
     else with_lb(lbv, [&](auto LB) { hmc_gauss_quad_kernel<D, false, decltype(LB)::value, 7><<<qgrid, 64, 0, s>>>(a, a.ws_logu); });
   }
+  else if (g_quad_prop && diag) hmc_gauss_quad_prop_kernel<D, true><<<qgrid, 64, 0, s>>>(a, a.ws_logu);
+  else if (g_quad_prop) hmc_gauss_quad_prop_kernel<D, false><<<qgrid, 64, 0, s>>>(a, a.ws_logu);
   else if (diag) hmc_gauss_quad_kernel<D, true, 0><<<qgrid, 64, 0, s>>>(a, a.ws_logu);
   else with_lb(lbv, [&](auto LB) { hmc_gauss_quad_kernel<D, false, decltype(LB)::value><<<qgrid, 64, 0, s>>>(a, a.ws_logu); });
   profile_end(s);

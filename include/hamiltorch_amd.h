@@ -586,7 +586,16 @@ int hta_jit_rmhmc_implicit_sample(void* module, const HtaCbRmhmcImpArgs* args, i
  * barriers - same records in the same places, bit-identical results; 0 = the 256-thread launch, the parity partner),
  * "quad_rows_wt" (1 default = the row wave of the "quad_local" / "quad_wide" launches stores the sample rows write-through at agent
  * scope, so they leave L2 while the launch runs and not in the write-back behind it - same values, same addresses; 0 = plain
- * stores, the parity partner). */
+ * stores, the parity partner),
+ * "quad_prop" (1 default = every launch form of the quad route applies a trajectory's two half kicks and L leapfrog steps as ONE
+ * linear map per eigen-coordinate, y = a yc + b z ; r = c yc + d z, whose coefficients are the same straight-line arithmetic run
+ * once per launch in float64 on two basis inputs (csrc/quad_prop.hpp) - four instructions instead of 2 L + 2, closer to the float64
+ * trajectory than the float32 chain of steps, the same results inside every oracle band, not bit for bit; the route strings stay
+ * what they are; 0 = the step-by-step instances, the parity partner; the per-step entry points hta_hmc_gaussian_leapfrog_* always
+ * step), "quad_prop_chains" (0 default; the chains per block of the "quad_prop" form of the "quad_lead" launch, 16, 8 or 4: fewer
+ * chains per block spread the drawing of the records over more compute units; 0 = 4 up to 1024 chains, 8 up to 2048, 16 beyond),
+ * "quad_prop_sweep" (0 default; the waves of that launch that draw behind its first full pass: 0 = waves 2-3, 1 = waves 2, 3, 6
+ * and 7, 2 = waves 2-7; same records in the same places whatever the value). */
 int hta_set_tuning(const char* key, int value);
 /* current value of a route key; every key back to its default (test fixtures call this between tests: the keys are
  * process-global).  The environment variable HTA_TUNING_DEFAULTS="key=value,..." moves the DEFAULT of the named keys for the
