@@ -1,3 +1,4 @@
+// HISTORY: last builds against commit 3376c1e (it includes rmhmc_metric_mfma.hip with -DHTA_TIMING=1, a switch that commit was the last to have).
 // Phase timer of metric_warm_mfma_kernel (developer tool): s_memtime stamps of workgroup 0 at the phase boundaries.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DHTA_TIMING=1 -ffp-contract=on -fno-slp-vectorize -x hip tools/scratch/metric_phase.cpp -x none \
 //         $(ls hamiltorch_amd/csrc/build/*.o | grep -v rmhmc_metric_mfma.o) -o tools/scratch/metric_phase.bin

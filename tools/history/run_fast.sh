@@ -1,3 +1,4 @@
+# HISTORY: last works against commit 3376c1e (runs metric_phase.bin, which needs the HTA_TIMING build of rmhmc_metric_mfma.hip).
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 ( ./tools/scratch/metric_phase.bin 100 256 0 1e-3 1 10 1 ) > gpurun_out/fast_phase_traj.txt 2>&1
