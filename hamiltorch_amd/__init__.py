@@ -16,3 +16,5 @@ from .util import set_random_seed  # noqa: F401
 from .models import GaussianTarget  # noqa: F401
 from . import samplers  # noqa: F401
 from . import diagnostics  # noqa: F401
+from . import adapt  # noqa: F401
+from .adapt import warmup  # noqa: F401

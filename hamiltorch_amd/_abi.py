@@ -126,6 +126,7 @@ def _sig(scalar):
         "hta_diag_lags": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp],
         "hta_diag_rank": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
         "hta_diag_rank_folded": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+        "hta_moments_update": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp],
     }
 
 
@@ -139,7 +140,8 @@ PLAIN_SYMBOLS = ["hta_abi_version", "hta_last_error", "hta_device_info", "hta_se
                  "hta_jit_rmhmc_workspace_bytes", "hta_jit_rmhmc_sample", "hta_jit_rmhmc_implicit_sample", "hta_jit_split_workspace_bytes", "hta_jit_split_sample",
                  "hta_jit_path_leapfrog", "hta_jit_rolled_sample",
                  "hta_diag_lag_block", "hta_diag_segment_rows", "hta_diag_workspace_bytes", "hta_diag_finish",
-                 "hta_diag_rank_tile", "hta_diag_rank_ndtri", "hta_diag_rank_workspace_bytes"]
+                 "hta_diag_rank_tile", "hta_diag_rank_ndtri", "hta_diag_rank_workspace_bytes",
+                 "hta_moments_workspace_bytes", "hta_moments_finish"]
 TYPED_SYMBOLS = sorted(_sig(c_f32).keys())
 
 
@@ -221,6 +223,9 @@ def load():
         lib.hta_diag_rank_ndtri.restype = c_f64
         lib.hta_diag_rank_workspace_bytes.argtypes = [c_i64, c_i64, c_i64, c_int]
         lib.hta_diag_rank_workspace_bytes.restype = c_i64
+        lib.hta_moments_workspace_bytes.argtypes = [c_i64, c_i64, c_i64]
+        lib.hta_moments_workspace_bytes.restype = c_i64
+        lib.hta_moments_finish.argtypes = [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp, c_vp]
         for suf, scalar in (("f32", c_f32), ("f64", c_f64)):
             for name, args in _sig(scalar).items():
                 fn = getattr(lib, "%s_%s" % (name, suf))

@@ -22,6 +22,15 @@ draws' scores and the 5 % / 95 % indicators go through the same stages:
 
     r = hamiltorch_amd.diagnostics.rank_summary(out, skip=1)
     r.ess_bulk, r.ess_tail, r.rhat, r.rhat_bulk, r.rhat_folded, r.q05, r.median, r.q95
+
+``RunningMoments`` is the streaming half (csrc/moments.hip): per-chain mean and M2 of every coordinate, updated chunk by chunk, for
+mean, sd, within / between variance and R-hat of runs that are never held in memory at once - and the pooled variance the
+cross-chain warm-up takes its diagonal mass from (hamiltorch_amd/adapt.py):
+
+    acc = hamiltorch_amd.diagnostics.RunningMoments()
+    acc.update(out, skip=1)                                                       # as often as chunks arrive
+    m = acc.result(reg_n=5)
+    m.mean, m.sd, m.var_within, m.var_between, m.var_total, m.rhat, m.inv_mass
 """
 from __future__ import annotations
 
@@ -388,3 +397,191 @@ def ess_tail(samples, skip=0, max_lag=None, workspace_bytes=256 << 20):
 def rhat_rank(samples, skip=0, workspace_bytes=256 << 20):
     """[D] rank-normalised R-hat of samples: the larger of the bulk and the folded statistic (see rank_summary)."""
     return rank_summary(samples, skip, LAG_BLOCK, workspace_bytes).rhat
+
+
+# ---- running moments (csrc/moments.hip) -------------------------------------------------------------------------------------
+#: rows of S per grid segment of the update kernel, its lower limit, the grid size below which segments are halved, the lanes
+#: of a workgroup, and the chain slices of the finish kernel (csrc/moments.hip: MOM_*)
+MOMENTS_SEGMENT_ROWS = 256
+MOMENTS_MIN_SEGMENT_ROWS = 32
+MOMENTS_TARGET_BLOCKS = 512
+MOMENTS_THREADS = 256
+MOMENTS_CHAIN_SLICES = 16
+
+
+def moments_segment_rows(S, C, D):
+    """Rows per segment of an update with a chunk x[S, C, D] (csrc/moments.hip: moments_segment_rows, restated).  Pure."""
+    bx = -(-int(C) * int(D) // MOMENTS_THREADS)
+    R = MOMENTS_SEGMENT_ROWS
+    while R > MOMENTS_MIN_SEGMENT_ROWS and bx * -(-int(S) // R) < MOMENTS_TARGET_BLOCKS:
+        R //= 2
+    return R
+
+
+class MomentsResult:
+    """Pooled statistics of a RunningMoments: [D] float64 tensors on the samples' device.  `mean`: the mean of the chain means;
+    `var_within`: the mean over chains of their unbiased variances; `var_between`: the unbiased variance of the chain means;
+    `var_total`: the unbiased variance of all draws of all chains around `mean`; `sd` = sqrt(var_total); `rhat`: R-hat of the
+    unsplit chains (stack() the accumulators of a run's halves for split R-hat); `inv_mass` ([D], `dtype`): the regularised
+    `var_total`, or None when no `reg_n` was given."""
+    __slots__ = ("mean", "sd", "var_within", "var_between", "var_total", "rhat", "inv_mass", "n_draws", "n_chains")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def max_rhat(self):
+        """max over coordinates of rhat, NaN coordinates ignored."""
+        v = self.rhat[~torch.isnan(self.rhat)]
+        return float(v.max()) if v.numel() else float("nan")
+
+    def to(self, device):
+        return MomentsResult(**{k: (getattr(self, k).to(device) if torch.is_tensor(getattr(self, k)) else getattr(self, k)) for k in self.__slots__})
+
+    def __repr__(self):
+        return "MomentsResult(%d draws x %d chains x %d coordinates)" % (self.n_draws, self.n_chains, self.mean.numel())
+
+
+class RunningMoments:
+    """Per-chain mean and M2 of every coordinate of samples that arrive chunk by chunk, in fp64 on the device (csrc/moments.hip):
+
+        acc = hamiltorch_amd.diagnostics.RunningMoments()
+        for _ in range(100):
+            out = hamiltorch_amd.sample(target, start, num_samples=50, ...)        # rows never held together
+            acc.update(out, skip=1)
+            start = out[-1]
+        r = acc.result()
+        r.mean, r.sd, r.rhat                                                        # [D] float64 tensors
+
+    `RunningMoments(C, D, device)` fixes the shape at once; without arguments the first update() does.  The state is
+    `state[2, C, D]` (means, M2) and the host integer `n_draws`.  CPU samples are staged to the GPU chunk by chunk like in
+    summary(), and the results of an accumulator fed from the CPU come back on the CPU."""
+
+    def __init__(self, C=None, D=None, device=None):
+        self.state, self.n_draws, self._host = None, 0, False
+        if (C is None) != (D is None):
+            raise ValueError("RunningMoments: give both C and D, or neither")
+        if C is not None:
+            if int(C) < 1 or int(D) < 1:
+                raise ValueError("RunningMoments: bad shape (C=%d D=%d)" % (C, D))
+            dev = torch.device("cuda" if device is None else device)
+            self._host = dev.type != "cuda"
+            if self._host:
+                from .host import _device
+                dev = _device()
+            self.state = torch.zeros((2, int(C), int(D)), dtype=torch.float64, device=dev)
+
+    @property
+    def n_chains(self):
+        return None if self.state is None else int(self.state.shape[1])
+
+    @property
+    def n_coordinates(self):
+        return None if self.state is None else int(self.state.shape[2])
+
+    def reset(self):
+        """Forget every draw (the shape stays)."""
+        self.n_draws = 0
+        return self
+
+    def update(self, samples, skip=0):
+        """Add the rows of `samples` after the first `skip` ([S, C, D] tensor, [S, D] tensor = one chain, the list sample()
+        returns - row 0 is params_init: skip=1 -, or a plain list of rows).  Returns self."""
+        x = _as_samples(samples)
+        skip = int(skip)
+        if skip < 0:
+            raise ValueError("RunningMoments: skip=%d" % skip)
+        S, C, D = x.shape[0] - skip, x.shape[1], x.shape[2]
+        if C < 1 or D < 1:
+            raise ValueError("RunningMoments: no chains or no coordinates in samples of shape %s" % (tuple(x.shape),))
+        if S < 1:
+            return self
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float32)
+        if not x.is_cuda:
+            from .host import _device
+            if self.state is None:
+                self._host = True
+            x = x.to(self.state.device if self.state is not None else _device())
+        _abi.require_device(x, "samples")
+        if self.state is None:
+            self.state = torch.empty((2, C, D), dtype=torch.float64, device=x.device)
+        if (C, D) != tuple(self.state.shape[1:]) or x.device != self.state.device:
+            raise ValueError("RunningMoments: samples of %d chains x %d coordinates on %s; the accumulator holds %d x %d on %s"
+                             % (C, D, x.device, self.state.shape[1], self.state.shape[2], self.state.device))
+        x = x[skip:]
+        if x.stride(2) != 1 or x.stride(1) < D or x.stride(0) < (C - 1) * x.stride(1) + D:
+            x = x.contiguous()
+        lib = _abi.load()
+        vp = ctypes.c_void_p
+        with torch.cuda.device(x.device):
+            nbytes = int(lib.hta_moments_workspace_bytes(S, C, D))
+            ws = _abi.scratch(x, nbytes, "moments")
+            _abi._check(getattr(lib, "hta_moments_update_" + _abi._suffix(x))(vp(x.data_ptr()), x.stride(0), x.stride(1), S, C, D, self.n_draws,
+                                                                             vp(self.state.data_ptr()), None if ws is None else vp(ws.data_ptr()), nbytes,
+                                                                             _abi._stream(x)), "hta_moments_update")
+        self.n_draws += S
+        return self
+
+    def merge(self, other):
+        """Add the draws another accumulator of the same chains has seen, chain by chain (Chan's formula; the counts may differ).
+        Returns self."""
+        if other.state is None or other.n_draws == 0:
+            return self
+        if self.state is None:
+            self.state, self._host = torch.empty_like(other.state), other._host
+        if self.state.shape != other.state.shape or self.state.device != other.state.device:
+            raise ValueError("RunningMoments.merge: %s on %s and %s on %s" % (tuple(self.state.shape[1:]), self.state.device,
+                                                                               tuple(other.state.shape[1:]), other.state.device))
+        if self.n_draws == 0:
+            self.state.copy_(other.state)
+        else:
+            na, nb = float(self.n_draws), float(other.n_draws)
+            delta = other.state[0] - self.state[0]
+            self.state[1] += other.state[1] + delta * delta * (na * nb / (na + nb))
+            self.state[0] += delta * (nb / (na + nb))
+            bad = ~(torch.isfinite(self.state[0]) & torch.isfinite(self.state[1]))
+            self.state[:, bad] = float("nan")
+        self.n_draws += other.n_draws
+        return self
+
+    @classmethod
+    def stack(cls, parts):
+        """A new accumulator whose chains are the chains of `parts` side by side (equal draw counts and coordinates).  Of the
+        accumulators of a run's first and last half it is the accumulator of the 2 C half chains: its rhat is split R-hat."""
+        parts = list(parts)
+        if not parts or any(p.state is None for p in parts):
+            raise ValueError("RunningMoments.stack: an accumulator without a shape")
+        if len({p.n_draws for p in parts}) != 1 or len({(p.state.shape[2], p.state.device) for p in parts}) != 1:
+            raise ValueError("RunningMoments.stack: the parts differ in draws, coordinates or device")
+        out = cls()
+        out.state = torch.cat([p.state for p in parts], dim=1).contiguous()
+        out.n_draws, out._host = parts[0].n_draws, all(p._host for p in parts)
+        return out
+
+    def result(self, reg_n=None, reg_floor=1e-3, dtype=None):
+        """The pooled statistics of the draws seen so far (a MomentsResult).  With `reg_n` also `inv_mass` of `dtype` (default
+        float32): var_total N / (N + reg_n) + reg_floor reg_n / (N + reg_n), N = n_draws x chains (Stan: reg_n = 5)."""
+        if self.state is None or self.n_draws < 1:
+            raise ValueError("RunningMoments.result: no draws yet")
+        lib = _abi.load()
+        _, C, D = self.state.shape
+        dev = self.state.device
+        mean, vw, vb, vt, rh = (torch.empty(D, dtype=torch.float64, device=dev) for _ in range(5))
+        im = None
+        if reg_n is not None:
+            dtype = torch.float32 if dtype is None else dtype
+            if dtype not in (torch.float32, torch.float64):
+                raise TypeError("RunningMoments.result: inv_mass in float32 or float64, got %s" % dtype)
+            im = torch.empty(D, dtype=dtype, device=dev)
+        vp = ctypes.c_void_p
+        p = lambda t: vp(t.data_ptr())                                           # noqa: E731
+        with torch.cuda.device(dev):
+            _abi._check(lib.hta_moments_finish(C, D, self.n_draws, p(self.state), p(mean), p(vw), p(vb), p(vt), p(rh),
+                                               0.0 if reg_n is None else float(reg_n), float(reg_floor),
+                                               p(im) if im is not None and im.dtype == torch.float32 else None,
+                                               p(im) if im is not None and im.dtype == torch.float64 else None,
+                                               _abi._stream(self.state)), "hta_moments_finish")
+        out = MomentsResult(mean=mean, sd=torch.sqrt(vt), var_within=vw, var_between=vb, var_total=vt, rhat=rh, inv_mass=im,
+                            n_draws=int(self.n_draws), n_chains=int(C))
+        return out.to("cpu") if self._host else out

@@ -676,6 +676,42 @@ int hta_diag_rank_folded_f32(const float* x, int64_t stride_s, int64_t stride_c,
 int hta_diag_rank_folded_f64(const double* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, const double* centre,
                              double* zf, int32_t* bad, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Running moments of samples that arrive chunk by chunk (symbols added under ABI 17; csrc/moments.hip): the per-chain mean and
+ * M2 = sum of squared deviations from it of every coordinate, in fp64, and from them the pooled statistics of all chains -
+ * the streaming half of the diagnostics above and the source of the warm-up's diagonal mass (hamiltorch_amd/adapt.py).
+ *
+ *   x            a chunk x[S, C, D], S >= 1: f32 / f64, the stride rules of hta_diag_*.  All arithmetic is fp64.
+ *   state        double[2][C][D], 8-byte aligned, owned by the caller: state[0] the means, state[1] the M2 of the n_prev draws
+ *                seen so far.  The count lives on the host: n_prev = 0 overwrites the state, and the caller adds S after a call.
+ *   update       per series (c, d) the chunk's mean and M2 by Welford's recurrence in row order (k = 1, 2, ...: delta = x - mean,
+ *                mean += delta / k, M2 += delta (x - mean)), over segments of R rows that are merged in segment order; then
+ *                Chan's merge into the state: delta = m_chunk - mean, mean += delta S / (n + S),
+ *                M2 += M2_chunk + delta^2 n S / (n + S).  R = 256, halved down to 32 while the grid stays below 512 workgroups.
+ *   workspace    >= hta_moments_workspace_bytes(S, C, D) bytes, 8-byte aligned: the segments' partial results.  0 bytes (the
+ *                pointer may then be NULL) when the chunk is one segment: one launch merges it straight into the state.
+ *   non-finite   a NaN or infinite draw (or an overflow of M2) leaves NaN in the mean and M2 of its own (c, d), for good, and
+ *                touches nothing else.
+ *   finish       hta_moments_finish: the pooled statistics of the n >= 1 draws per chain in `state`, [D] outputs in device
+ *                memory, any of them NULL: mean = mean of the chain means; var_within = mean over chains of M2 / (n - 1);
+ *                var_between = unbiased variance of the chain means (0 for C == 1);
+ *                var_total = (sum_c M2 + n sum_c (m_c - mean)^2) / (n C - 1); rhat = sqrt(((n - 1) / n W + B) / W) with W =
+ *                var_within, B = var_between (inf for W <= 0 < B, NaN for W <= 0 = B or n < 2: ess.py's rhat_split on unsplit
+ *                chains).  inv_mass_f32 / inv_mass_f64 receive Stan's shrinkage of the pooled variance,
+ *                var_total N / (N + reg_n) + reg_floor reg_n / (N + reg_n), N = n C, in the sampler's dtype.
+ *   determinism  no floating-point atomics; every sum runs in an order fixed by (S, C, D): equal bits for equal input and equal
+ *                chunking, whatever the strides.
+ * Bad shapes, NULL pointers and short workspaces return HTA_ERR_INVALID before any launch; like every call here these only
+ * enqueue work on `stream`.  hta_last_route() names the update kernel ("moments_update_kernel<float>"). */
+int64_t hta_moments_workspace_bytes(int64_t S, int64_t C, int64_t D);
+int hta_moments_update_f32(const float* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, int64_t n_prev, double* state,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+int hta_moments_update_f64(const double* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, int64_t n_prev, double* state,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+int hta_moments_finish(int64_t C, int64_t D, int64_t n, const double* state, double* mean, double* var_within, double* var_between,
+                       double* var_total, double* rhat, double reg_n, double reg_floor, float* inv_mass_f32, double* inv_mass_f64,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
