@@ -1,6 +1,7 @@
 // libhamiltorch_amd.so: ABI version, error channel, device query, tuning knobs.
 #include <stdarg.h>
 #include "common.hpp"
+#include "rmhmc.hpp"
 
 namespace hta {
 static thread_local char g_err[512] = "";
@@ -20,23 +21,12 @@ void note_route(const char* fmt, ...) {
 }
 int g_small_chains_per_block = 0;  // 0 = default (64)
 int g_force_general = 0;
-int g_rmhmc_batch = 1;     // fused RMHMC: 16 chains per workgroup on the matrix cores from 2048 chains on (0 off, 2 always)
-int g_rmhmc_momwave = 1;   // fused RMHMC: momentum draws by the wave-per-task kernel (fp32, jitter, D <= 104); 0: workgroup-per-task kernel
-int g_rmhmc_mfma4 = 1;     // fused RMHMC: four chains per workgroup on v_mfma_f32_4x4x1_16b (0 off, 1 for lo <= chains < hi, 2 always)
-int g_rmhmc_mfma4_lo = 1793, g_rmhmc_mfma4_hi = 2049;   // round 4: up to 7 x CUs chains the two-chain kernel of rmhmc_uvc.hip, two workgroups per CU (1536 chains: 2.25e8 against 1.97e8); before:   // round 2 (tracked products): 544 / 640 / 700 chains 1.40x / 1.37x / 1.38x the one-chain kernel, below 513 rmhmc_uv_kernel; round 1: 3072: 0.87x, 4096: 0.88x the 16-chain kernel (a third workgroup per CU doubles a SIMD's load)
 int g_netn_waves = 1;        // csrc/netn_hmc.hip: waves per chain (2 / 4 where they fit; measured slower at 1024 chains)
-int g_rmhmc_uv = 1;          // rmhmc_uv.hip (one or two chains per workgroup as columns of the matrix instruction): 1 up to 2 x CUs chains, 0 off, 2 always
-int g_rmhmc_pair = 1;        // four-chain kernels: consecutive half steps share product phases (0: one half step at a time)
-int g_rmhmc_overlap = 0;   // fused RMHMC: 1 = momentum draws of the next block of trajectories on a side stream (round 3: off -
-                           // run beside the trajectory kernel the draws slow it by a third; serial is 3-8 % faster at every chain count)
-int g_rmhmc_momsplit = 1;  // fused RMHMC with jitter: p = chol(P) z1 + sqrt(jitter u) . z2 (exactly N(0, P + diag(jitter u)) like
-                           // chol(P + diag(jitter u)) z, without a Cholesky per draw); 0 = the per-draw factorisation
 int g_gauss_eig = 1;       // small-D identity-mass Gaussian HMC integrates in the eigenbasis of P (0: direct kernel, 2: chain per lane only)
 int g_fill_blocks = 4096;        // grid cap of the pre-draw pass (256-thread blocks, grid-stride)
 int g_quad_max_chains = 65536;   // up to here a chain takes a DPP quad (one eigen-coordinate per lane), beyond a lane
 int g_quad_variant = 7;          // instance of the quad kernel (hmc_gauss_quad_dev.hpp: VAR); 0 = the round-1 instance, 3 = uniform-base addressing + no NaN guard, 7 = + fused row / butterfly block
-int g_rmhmc_fused = 1;           // 0 = per-evaluation Jacobi path, 3 = fused with two chains per workgroup (parity tests)
-extern int g_metric_mfma, g_metric_general, g_metric_traj, g_metric_second, g_metric_bx3, g_metric_resident, g_metric_select, g_metric_sqrtdraw, g_rmhmc_wide, g_rmhmc_uv_co, g_rmhmc_uv_g, g_rmhmc_uvc, g_quad_fused, g_quad_producers, g_quad_chunks, g_quad_starve, g_quad_rows, g_quad_local, g_quad_wide, g_quad_rows_wt, g_quad_lead, g_quad_wide_launches, g_quad_prop, g_quad_prop_sweep, g_quad_prop_chains;         // rmhmc_metric_mfma.hip, rmhmc_fused.hip
+extern int g_metric_second, g_metric_bx3, g_metric_sqrtdraw, g_rmhmc_uvc, g_quad_fused, g_quad_producers, g_quad_chunks, g_quad_starve, g_quad_rows, g_quad_local, g_quad_wide, g_quad_rows_wt, g_quad_lead, g_quad_wide_launches, g_quad_prop, g_quad_prop_sweep, g_quad_prop_chains;         // rmhmc_metric_mfma.hip, rmhmc_uvc.hip, hmc_gaussian.hip (the other metric keys and every fused-RMHMC key: rmhmc.hpp)
 int g_mlp_valu = 0;               // 1 = keep the Bayesian-MLP sampler on the VALU kernel (parity tests of both)
 int g_mlp3_route = 1;             // csrc/mlp3_mfma.hip (two wide hidden layers on the matrix cores); 0 = such models stay on the callback path
 

@@ -56,16 +56,17 @@ int mh_select(T* cur, const T* prop, const T* init, const T* Ho, const T* Hn, co
 void profile_begin(hipStream_t s);
 void profile_end(hipStream_t s);
 
-// rmhmc_fused.hip: the identity-soft-abs fast path of the Gaussian-target sampler
+// rmhmc_fused.hip: the identity-soft-abs fast path of the Gaussian-target sampler (its tuning keys are defined at the top of that file)
 extern int g_rmhmc_fused;                                   // tuning key "rmhmc_fused" (default 1)
 extern int g_rmhmc_batch;                                   // tuning key "rmhmc_batch" (default 1)
 extern int g_rmhmc_momwave;                                 // tuning key "rmhmc_momwave" (default 1)
-extern int g_rmhmc_uv;                                      // tuning key "rmhmc_uv" (default 1: rmhmc_uv.hip up to 2 x CUs chains; 0 off; 2 always)
 extern int g_rmhmc_pair;                                    // tuning key "rmhmc_pair" (default 1: two half steps per K + 2 product phases)
 extern int g_rmhmc_mfma4, g_rmhmc_mfma4_lo, g_rmhmc_mfma4_hi;    // tuning keys "rmhmc_mfma4" (default 1), "rmhmc_mfma4_lo", "rmhmc_mfma4_hi"
 extern int g_rmhmc_overlap;                                 // tuning key "rmhmc_overlap" (default 0 since round 3)
-extern int g_rmhmc_uv_co, g_rmhmc_uv_g;                    // tuning keys "rmhmc_uv_co" / "rmhmc_uv_g" (rmhmc_uv.hip)
 extern int g_rmhmc_momsplit;                                // tuning key "rmhmc_momsplit" (default 1): p = chol(P) z1 + sqrt(e) z2
+extern int g_rmhmc_wide;                                    // tuning key "rmhmc_wide" (default 1)
+extern int g_rmhmc_uv;                                      // tuning key "rmhmc_uv" (default 1: rmhmc_uv.hip up to 2 x CUs chains; 0 off; 2 always)
+extern int g_rmhmc_uv_co, g_rmhmc_uv_g;                    // tuning keys "rmhmc_uv_co" / "rmhmc_uv_g" (all three: rmhmc_uv.hip)
 template <typename T>
 int fused_plan(const T* lam0_host, int D, int metric, double alpha, int has_jitter, double jitter, double* logdetP, int* series);
 template <typename T> int inverse_from_eigen(const T* V0, const T* lam0, T* S, int D, hipStream_t s);

@@ -1,6 +1,8 @@
 // Device-side pieces shared by the whole-trajectory RMHMC kernels of the Gaussian-target fast path
-// (rmhmc_fused.hip: one / four / sixteen chains per workgroup, the latter two on the body of rmhmc_rows4_dev.hpp; rmhmc_uv.hip,
-// rmhmc_uvc.hip: one or two chains per workgroup as columns of the matrix instruction, on the shell of rmhmc_cols_dev.hpp).
+// (rmhmc_fused.hip, the launcher of: rmhmc_fused_chain_dev.hpp, one chain per workgroup, on the Cholesky of rmhmc_fused_chol_dev.hpp;
+// rmhmc_fused_tiles_dev.hpp, four / sixteen chains per workgroup on the body of rmhmc_rows4_dev.hpp; rmhmc_fused_momentum_dev.hpp, the
+// momentum draws ahead of them.  rmhmc_uv.hip, rmhmc_uvc.hip: one or two chains per workgroup as columns of the matrix instruction, on
+// the shell of rmhmc_cols_dev.hpp).
 #pragma once
 #include <utility>
 #include "common.hpp"

@@ -1,7 +1,7 @@
 // The trajectory body of the explicit-RMHMC kernels whose lanes own FOUR consecutive rows of one chain's vectors - one Philox
-// block of jitter per evaluation - and whose products run on the matrix cores (rmhmc_fused.hip: rmhmc_batch_kernel, sixteen
-// chains per workgroup; rmhmc_mfma4_kernel, four).  Same streams, same update order and barriers per pass as the one-chain
-// rmhmc_fused_kernel, which is the parity reference of both.
+// block of jitter per evaluation - and whose products run on the matrix cores (rmhmc_fused_tiles_dev.hpp: rmhmc_batch_kernel, sixteen
+// chains per workgroup; rmhmc_mfma4_kernel, four; launched by rmhmc_fused.hip).  Same streams, same update order and barriers per pass
+// as the one-chain rmhmc_fused_kernel (rmhmc_fused_chain_dev.hpp), which is the parity reference of both.
 //
 // The algorithm is written once here, over a per-kernel Tile that holds what really differs between the kernels:
 //   NC, MSZ                       chains per workgroup; floats per LDS vector matrix

@@ -1,5 +1,6 @@
 // Explicit RMHMC for a Gaussian target on the identity-soft-abs path (see rmhmc_fused.hip for why that path exists and what
-// it computes: hamiltorch/samplers.py:969-1026 with the integrator S:425-461), ONE or TWO chains per workgroup on the matrix
+// it computes: hamiltorch/samplers.py:969-1026 with the integrator S:425-461; its launcher, rmhmc_fused_sample, hands over to
+// rmhmc_uv_launch below, and the one-chain VALU kernel these are measured against is rmhmc_fused_chain_dev.hpp's), ONE or TWO chains per workgroup on the matrix
 // cores, for every chain count up to 2 x (compute units): rmhmc_uv_kernel<G, CO>, and the dispatch to its successors in
 // rmhmc_uvc.hip (rmhmc_uvc_kernel: one-chain groups with K == 2 and jitter; rmhmc_uvc2_kernel: two-chain groups), which leaves
 // this kernel the one-chain groups without jitter or with K != 2.
@@ -131,6 +132,7 @@ __global__ __launch_bounds__(XNT, CO ? 2 : 1) void rmhmc_uv_kernel(FusedArgs<flo
   cols_trajectories(a, t);
 }
 
+int g_rmhmc_uv = 1;          // rmhmc_uv.hip (one or two chains per workgroup as columns of the matrix instruction): 1 up to 2 x CUs chains, 0 off, 2 always
 int g_rmhmc_uv_co = 1;       // tuning key "rmhmc_uv_co" (default 1): the 256-register instances, two workgroups per CU; 0 = the uncapped ones
 int g_rmhmc_uv_g = 0;        // tuning key "rmhmc_uv_g": chains per workgroup (0 = by chain count, 1, 2)
 

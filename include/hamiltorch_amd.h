@@ -291,7 +291,7 @@ int hta_rmhmc_gaussian_leapfrog_f64(double* theta, double* p, double* theta_copy
  * launch of `n_traj` trajectories; arguments as hta_hmc_gaussian_sample.  workspace:
  * hta_rmhmc_workspace_bytes(C, D, sizeof(T)) bytes at least (required; ABI 10: includes the metric evaluations' slabs for sizes
  * beyond one CU's LDS, hta_metric_eval_workspace_bytes).  Every further C*D*sizeof(T) bytes let the
- * fused path (soft-abs map == identity on the target's spectrum, csrc/rmhmc_fused.hip) draw the momenta of one more
+ * fused path (soft-abs map == identity on the target's spectrum: csrc/rmhmc_fused.hip, its kernels in csrc/rmhmc_fused_*_dev.hpp) draw the momenta of one more
  * trajectory per pass ahead of the chains (one full-chip batch of draws); with the minimum it works in passes of 4.  With
  * hta_set_tuning("rmhmc_overlap", 1) and room for >= 16 trajectories the draws of the next block run on an internal side
  * stream (forked from and joined back into `stream` inside the call) under the trajectories of the current one.

@@ -1,5 +1,6 @@
 """Cases for the trajectory-mode tests of the explicit-RMHMC kernels for Gaussian targets - rmhmc_fused_kernel<T,KH,1|2,tracked>,
-rmhmc_fused_kernel_wide<56|64>, rmhmc_mfma4_kernel, rmhmc_batch_kernel<25|28> (hamiltorch_amd/csrc/rmhmc_fused.hip), rmhmc_uv_kernel<G,
+rmhmc_fused_kernel_wide<56|64> (hamiltorch_amd/csrc/rmhmc_fused_chain_dev.hpp), rmhmc_mfma4_kernel, rmhmc_batch_kernel<25|28>
+(rmhmc_fused_tiles_dev.hpp; all of them launched by rmhmc_fused.hip, after the draws of rmhmc_fused_momentum_dev.hpp), rmhmc_uv_kernel<G,
 co|solo> (rmhmc_uv.hip), rmhmc_uvc_kernel and rmhmc_uvc2_kernel (rmhmc_uvc.hip) - and the driver that runs oracle/hmc_oracle.py on
 them.  Plain numpy, no GPU, nothing of the library on the reference side.  Shared by tests/test_rmhmc_traj_cases_cpu.py (which checks
 on the oracle alone that every case can tell a wrong kernel from a right one, and the launcher's rules restated here against the

@@ -631,16 +631,17 @@ def test_fused_workspace_passes_are_equivalent(ht):
     assert np.abs(outs[0][0][-1] - outs[0][0][0]).max() > 1e-3
 
 
-@pytest.mark.parametrize("split", [1, 0])
+@pytest.mark.parametrize("draw", [pytest.param("split", id="1"), pytest.param("wave", id="0"), "workgroup"])
 @pytest.mark.parametrize("T", [32, 75, 200])
-def test_fused_momentum_overlap_equals_serial(ht, T, split):
+def test_fused_momentum_overlap_equals_serial(ht, T, draw):
     """hta_set_tuning('rmhmc_overlap', 1): with room for two blocks the momentum draws of block b+1 run on a side stream under
     the trajectories of block b (the default, 0, keeps everything on the caller's stream - measured faster at every chain
     count, profiles/r03h_*).  Same kernels, same draws: bit-identical samples / reject counts, also when the call is repeated
-    back to back (event reuse) and followed by work on the caller's stream that reads the results; with the split draw
-    and with the factorisation per draw."""
+    back to back (event reuse) and followed by work on the caller's stream that reads the results; with each of the three
+    draw kernels the launcher chooses between: the split draw, the factorisation per draw on one wave ("rmhmc_momsplit" = 0)
+    and on a workgroup ("rmhmc_momsplit" = 0, "rmhmc_momwave" = 0)."""
     from hamiltorch_amd import _abi
-    _abi.set_tuning("rmhmc_momsplit", split)
+    _abi.set_tuning("rmhmc_momsplit", 1 if draw == "split" else 0)
     D, C, L = 24, 40, 2
     t, _ = cfg3_target(ht, D, torch.float32, seed=9)
     th0 = tt((0.3 * O.philox_normals(3, np.arange(C), 0, D, O.PURPOSE_INIT, dtype=np.float64)).astype(np.float32), torch.float32)
@@ -648,6 +649,8 @@ def test_fused_momentum_overlap_equals_serial(ht, T, split):
     for mode in (1, 0):
         _abi.set_tuning("rmhmc_overlap", mode)
         try:
+            if draw == "workgroup":
+                _abi.set_tuning("rmhmc_momwave", 0)
             res = []
             for rep in range(2):
                 cur = th0.clone(); rej = torch.zeros(C, dtype=torch.int32, device=dev())
@@ -658,6 +661,7 @@ def test_fused_momentum_overlap_equals_serial(ht, T, split):
                 res.append((samples.sum(dim=0).cpu().numpy(), samples.cpu().numpy(), rej.cpu().numpy()))   # no explicit sync
         finally:
             _abi.set_tuning("rmhmc_overlap", 0)
+            _abi.set_tuning("rmhmc_momwave", 1)
         outs.append(res)
     for a_, b_ in zip(outs[0], outs[1]):
         for x, y in zip(a_, b_):

@@ -1,5 +1,6 @@
 """GPU parity of the explicit-RMHMC kernels for Gaussian targets in TRAJECTORY mode - rmhmc_fused_kernel<T,KH,1|2,tracked>,
-rmhmc_fused_kernel_wide<56|64>, rmhmc_mfma4_kernel, rmhmc_batch_kernel<25|28> (hamiltorch_amd/csrc/rmhmc_fused.hip), rmhmc_uv_kernel<G,
+rmhmc_fused_kernel_wide<56|64>, rmhmc_mfma4_kernel, rmhmc_batch_kernel<25|28> (hamiltorch_amd/csrc/rmhmc_fused.hip and the
+rmhmc_fused_*_dev.hpp it includes), rmhmc_uv_kernel<G,
 co|solo> (rmhmc_uv.hip), rmhmc_uvc_kernel and rmhmc_uvc2_kernel (rmhmc_uvc.hip), behind the three momentum kernels - against
 oracle/hmc_oracle.py:sample_rmhmc_explicit in float64 on the same Philox draws, through _abi.rmhmc_gaussian_sample directly: cur,
 theta_init, the workspace, H_old / H_new / accept / reject_count, traj_offset and chain_offset are the test's.  Cases, reference,

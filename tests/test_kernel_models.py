@@ -5,7 +5,7 @@ import pytest
 
 
 def wave_cholesky_model(P, ev, z, NB):
-    """rmhmc_momentum_wave_kernel (csrc/rmhmc_fused.hip) in numpy, lane for lane: lane (ty, tx) owns the elements
+    """rmhmc_momentum_wave_kernel (csrc/rmhmc_fused_momentum_dev.hpp) in numpy, lane for lane: lane (ty, tx) owns the elements
     (ty + 8a, tx + 8b), b <= a; rows / columns >= D are CLAMPED copies of P; panels of 4 columns pass through `pan` / `pan2`;
     p = L z is accumulated while the panels finish."""
     D = P.shape[0]

@@ -1,3 +1,4 @@
+# RETIRED with the HTA_RM_TIMING switch of rmhmc_fused.hip: f17df1c is the last commit whose source can be built with -DHTA_RM_TIMING=1 (the cycle counters hta_rm_dbg_read returns); the kernel-ms part below still runs against any library.
 """Developer timing of the fused explicit-RMHMC kernel (cfg3 shape): kernel ms per trajectory for a few (L, jitter)."""
 import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
