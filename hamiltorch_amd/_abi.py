@@ -127,6 +127,7 @@ def _sig(scalar):
         "hta_diag_rank": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
         "hta_diag_rank_folded": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
         "hta_moments_update": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp],
+        "hta_cov_update": [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp],
     }
 
 
@@ -141,7 +142,8 @@ PLAIN_SYMBOLS = ["hta_abi_version", "hta_last_error", "hta_device_info", "hta_se
                  "hta_jit_path_leapfrog", "hta_jit_rolled_sample",
                  "hta_diag_lag_block", "hta_diag_segment_rows", "hta_diag_workspace_bytes", "hta_diag_finish",
                  "hta_diag_rank_tile", "hta_diag_rank_ndtri", "hta_diag_rank_workspace_bytes",
-                 "hta_moments_workspace_bytes", "hta_moments_finish"]
+                 "hta_moments_workspace_bytes", "hta_moments_finish",
+                 "hta_cov_workspace_bytes", "hta_cov_state_bytes", "hta_cov_finish"]
 TYPED_SYMBOLS = sorted(_sig(c_f32).keys())
 
 
@@ -226,6 +228,11 @@ def load():
         lib.hta_moments_workspace_bytes.argtypes = [c_i64, c_i64, c_i64]
         lib.hta_moments_workspace_bytes.restype = c_i64
         lib.hta_moments_finish.argtypes = [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp, c_vp]
+        lib.hta_cov_workspace_bytes.argtypes = [c_i64, c_i64, c_i64]
+        lib.hta_cov_workspace_bytes.restype = c_i64
+        lib.hta_cov_state_bytes.argtypes = [c_i64, c_i64]
+        lib.hta_cov_state_bytes.restype = c_i64
+        lib.hta_cov_finish.argtypes = [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp, c_vp]
         for suf, scalar in (("f32", c_f32), ("f64", c_f64)):
             for name, args in _sig(scalar).items():
                 fn = getattr(lib, "%s_%s" % (name, suf))

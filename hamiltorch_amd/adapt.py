@@ -1,5 +1,5 @@
-"""Cross-chain warm-up: one step size and a diagonal mass for a batch of chains, from block-wise acceptance rates and the
-running moments of the chains' own draws.
+"""Cross-chain warm-up: one step size and a diagonal or dense mass for a batch of chains, from block-wise acceptance rates and
+the running moments (or, for the dense mass, the running covariance) of the chains' own draws.
 
     r = hamiltorch_amd.warmup(log_prob, start, num_steps_per_sample=10, step_size=0.01, seed=1)
     out = hamiltorch_amd.sample(log_prob, r.params, step_size=r.step_size, inv_mass=r.inv_mass, num_samples=1000, ...)
@@ -16,6 +16,13 @@ before: the first block runs at `carried` and the shrink point is log(carried), 
 update that point sends the first block to a step size ten times too long, acceptance 0, and the few blocks of a phase do not
 recover from it.
 
+`mass="dense"` (Controller, warmup): the windows' draws go into a `diagnostics.RunningCovariance` and the mass becomes their
+regularised pooled covariance, a (D, D) matrix - for targets whose badly scaled axes are not the coordinate axes.  With it the
+target is close to a unit Gaussian in the mass's coordinates, where L leapfrog steps of size eps turn every coordinate by the
+same angle L * 2 asin(eps / 2).  Near a multiple of pi the trajectory ends where it began (or at its mirror image) and the
+chain stops mixing however good the mass is: at eps = 1.17 and L = 10 the angle is 3.98 pi.  Choose L for the runs after a
+dense warm-up with that angle in mind - a short trajectory (L = 2 or 3) is usually right once the mass is dense.
+
 `Controller` is plain Python (no device, no library): `warmup_with` drives it with any `run_block` - a lambda around
 `sample_model`, or the CPU oracle in tests/test_adapt_cpu.py; `warmup` is `warmup_with` around `sample()`.
 """
@@ -28,16 +35,36 @@ WarmupResult = namedtuple("WarmupResult", "params step_size inv_mass history")
 
 
 def _mass_check(inv_mass, previous):
-    """(mass to use, accepted) for a window's new inv_mass: refused when an entry is not finite or not positive.  A device
-    tensor is checked and replaced on the device (`accepted` is then a 0-d bool tensor: nothing is read back); anything else
-    on the host."""
+    """(mass to use, accepted) for a window's new inv_mass: a (D,) mass is refused when an entry is not finite or not positive,
+    a (D, D) mass when an entry is not finite or the matrix is not positive definite (its Cholesky factorisation fails); the
+    mass kept instead is `previous`, for a matrix without one the identity.  A device tensor is checked and replaced on the
+    device (`accepted` is then a 0-d bool tensor: nothing is read back); anything else on the host."""
+    dense = getattr(inv_mass, "ndim", 1) == 2
     if getattr(inv_mass, "is_cuda", False):
         import torch
+        if dense:
+            eye = torch.eye(inv_mass.shape[0], dtype=inv_mass.dtype, device=inv_mass.device)
+            finite = torch.isfinite(inv_mass).all()
+            ok = finite & (torch.linalg.cholesky_ex(torch.where(finite, inv_mass, eye)).info == 0)
+            return torch.where(ok, inv_mass, eye if previous is None else previous), ok
         ok = (torch.isfinite(inv_mass) & (inv_mass > 0)).all()
         keep = torch.ones_like(inv_mass) if previous is None else previous
         return torch.where(ok, inv_mass, keep), ok
     import numpy as np
     v = np.asarray(inv_mass.detach().cpu() if hasattr(inv_mass, "detach") else inv_mass, dtype=np.float64)
+    if dense:
+        ok = bool(v.size) and v.shape[0] == v.shape[1] and bool(np.all(np.isfinite(v)))
+        if ok:
+            try:
+                np.linalg.cholesky(v)
+            except np.linalg.LinAlgError:
+                ok = False
+        if ok or previous is not None:
+            return (inv_mass if ok else previous), ok
+        if hasattr(inv_mass, "detach"):
+            import torch
+            return torch.eye(v.shape[0], dtype=inv_mass.dtype), ok
+        return np.eye(v.shape[0], dtype=getattr(inv_mass, "dtype", np.float64)), ok
     ok = bool(v.size) and bool(np.all(np.isfinite(v) & (v > 0)))
     return (inv_mass if ok else previous), ok
 
@@ -47,12 +74,16 @@ class Controller:
     collect) or None at the end; run it; `observe_block(accept_rate)` with the block's acceptance rate averaged over chains;
     when `window_due` is set, `observe_window(inv_mass)` with the regularised pooled variance of the window's collected draws
     before the next block.  `seed_index` counts the blocks 0, 1, 2, ...: a block is a sampling call of its own and needs its
-    own random stream.  `step_size` / `inv_mass`: the current values - after the last block the result.  `history`: one dict
+    own random stream.  `mass`: "diag" - observe_window takes a (D,) variance - or "dense" - a (D, D) covariance.
+    `step_size` / `inv_mass`: the current values - after the last block the result.  `history`: one dict
     per block (kind="block", phase, index, step_size, accept_rate, eps_bar) and per window (kind="window", phase, accepted,
     whatever observe_window was told)."""
 
     def __init__(self, step_size, block=10, windows=(5, 5, 10, 20), settle=5, desired_accept_rate=0.8, adapt_mass=True,
-                 reg_n=5, reg_floor=1e-3):
+                 reg_n=5, reg_floor=1e-3, mass="diag"):
+        if mass not in ("diag", "dense"):
+            raise ValueError("adapt.Controller: mass=%r; \"diag\" or \"dense\"" % (mass,))
+        self.mass = mass
         self.block, self.windows, self.settle = int(block), tuple(int(w) for w in windows), int(settle)
         if not float(step_size) > 0.0:
             raise ValueError("adapt.Controller: step_size=%r" % (step_size,))
@@ -113,6 +144,8 @@ class Controller:
     def observe_window(self, inv_mass, **record):
         if not self.window_due:
             raise RuntimeError("adapt.Controller: no window has just ended")
+        if getattr(inv_mass, "ndim", None) != (2 if self.mass == "dense" else 1):
+            raise ValueError("adapt.Controller: mass=%r takes a %s inv_mass" % (self.mass, "(D, D)" if self.mass == "dense" else "(D,)"))
         self.inv_mass, ok = _mass_check(inv_mass, self.inv_mass)
         self.history.append(dict(kind="window", phase=self.phase - 1, accepted=ok, **record))
         self.window_due = False
@@ -129,11 +162,15 @@ def _mean_rate(rate):
 def warmup_with(run_block, params_init, controller, moments_factory=None):
     """Drive `controller` with `run_block(params[C, D], n, step_size, inv_mass, seed_index)` -> (rows, accept_rate[C]): rows as
     sample() returns them - rows[0] is `params`, rows[1:] the block's draws, rows[-1] the next block's start.  The draws of a
-    window go into a fresh `moments_factory()` (default diagnostics.RunningMoments; anything with update(rows, skip) and
-    result(reg_n, reg_floor, dtype) -> .inv_mass, .sd, .rhat, .n_draws), whose regularised pooled variance becomes the mass.
+    window go into a fresh `moments_factory()` (default diagnostics.RunningMoments, under controller.mass == "dense"
+    diagnostics.RunningCovariance; anything with update(rows, skip) and result(reg_n, reg_floor, dtype) -> .inv_mass, .sd,
+    .rhat, .n_draws), whose regularised pooled variance - or covariance - becomes the mass.
     Returns WarmupResult(params, step_size, inv_mass, history)."""
     if moments_factory is None:
-        from .diagnostics import RunningMoments as moments_factory
+        if controller.mass == "dense":
+            from .diagnostics import RunningCovariance as moments_factory
+        else:
+            from .diagnostics import RunningMoments as moments_factory
     params, acc = params_init, None
     while True:
         blk = controller.next_block()
@@ -154,7 +191,8 @@ def warmup_with(run_block, params_init, controller, moments_factory=None):
 
 
 def warmup(log_prob_func, params_init, num_steps_per_sample=10, step_size=0.1, *, seed=None, chain_offset=0, block=10,
-           windows=(5, 5, 10, 20), settle=5, desired_accept_rate=0.8, adapt_mass=True, reg_n=5, reg_floor=1e-3, **sample_kwargs):
+           windows=(5, 5, 10, 20), settle=5, desired_accept_rate=0.8, adapt_mass=True, reg_n=5, reg_floor=1e-3, mass="diag",
+           **sample_kwargs):
     """Warm-up of `sample(log_prob_func, params_init, ...)` with Sampler.HMC (any of its integrators; a list of callables under
     the split ones): block k is sample(..., num_samples=block, burn=0, seed=seed + k) from where block k - 1 ended.  A (D,)
     `params_init` is one chain; a start on the host is staged once and the result comes back on the host.  `sample_kwargs`:
@@ -163,28 +201,41 @@ def warmup(log_prob_func, params_init, num_steps_per_sample=10, step_size=0.1, *
 
         sample(log_prob_func, r.params, step_size=r.step_size, inv_mass=r.inv_mass, ...)
 
-    One host read per block (its acceptance rate), none per window."""
+    `mass="diag"`: inv_mass is the (D,) pooled variance; one host read per block (its acceptance rate), none per window.
+    `mass="dense"`: inv_mass is the (D, D) pooled covariance from diagnostics.RunningCovariance (D <= COVARIANCE_MAX_D); the
+    window's matrix is checked on the device without a read-back, but every block's sample() call inverts and factors the
+    matrix through torch, and those calls read a status back - the one-read-per-block statement holds for "diag" only.  After
+    a dense warm-up the target is close to a unit Gaussian in the mass's coordinates and a trajectory turns every coordinate
+    by the same angle L * 2 asin(step_size / 2): pick L for the runs that follow so that this angle stays away from
+    multiples of pi, or the chains return to where they started (the module docstring)."""
     import torch
     from . import util
     from .enums import Sampler
     from .samplers import sample
     sampler = sample_kwargs.pop("sampler", Sampler.HMC)
     if sampler != Sampler.HMC:
-        raise ValueError("adapt.warmup: sampler=%s; the warm-up adapts the step size and the diagonal mass of Sampler.HMC - RMHMC takes its "
+        raise ValueError("adapt.warmup: sampler=%s; the warm-up adapts the step size and the mass of Sampler.HMC - RMHMC takes its "
                          "metric from the target's curvature and HMC_NUTS adapts a step size of its own in its burn-in" % (sampler,))
+    if mass not in ("diag", "dense"):
+        raise ValueError("adapt.warmup: mass=%r; \"diag\" or \"dense\"" % (mass,))
     for k in ("num_samples", "burn", "inv_mass", "debug", "verbose", "store_on_GPU"):
         if k in sample_kwargs:
             raise ValueError("adapt.warmup: %s is set by the warm-up itself" % k)
     if not torch.is_tensor(params_init) or params_init.dim() not in (1, 2):
         raise ValueError("adapt.warmup: params_init must be a (D,) or (C, D) tensor")
     one, host = params_init.dim() == 1, not params_init.is_cuda
+    if mass == "dense":
+        from .diagnostics import COVARIANCE_MAX_D
+        if params_init.shape[-1] > COVARIANCE_MAX_D:
+            raise ValueError("adapt.warmup: mass=\"dense\" keeps D (D + 1) / 2 co-moments per chain and is limited to D <= %d; D=%d"
+                             % (COVARIANCE_MAX_D, params_init.shape[-1]))
     theta = params_init.detach().reshape(1, -1) if one else params_init.detach()
     if host:
         from .host import _device, lift_callable
         theta = theta.to(_device())
         log_prob_func = lift_callable(log_prob_func, theta)
     seed = util.next_stream_seed() if seed is None else int(seed)
-    ctl = Controller(step_size, block, windows, settle, desired_accept_rate, adapt_mass, reg_n, reg_floor)
+    ctl = Controller(step_size, block, windows, settle, desired_accept_rate, adapt_mass, reg_n, reg_floor, mass=mass)
 
     def run_block(params, n, eps, inv_mass, k):
         return sample(log_prob_func, params, num_samples=n, num_steps_per_sample=num_steps_per_sample, step_size=eps, burn=0,

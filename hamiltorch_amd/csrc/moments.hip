@@ -20,6 +20,7 @@
 // bits, whatever the strides.  A non-finite draw (or an overflow) leaves NaN in the mean and M2 of its own (c, d) and nowhere else.
 // Nothing here allocates or synchronises.
 #include "common.hpp"
+#include "moments_rows.hpp"
 
 // every product and sum rounded on its own (the Makefile's -ffp-contract=on would fuse them): the recurrences below are then
 // the IEEE operations of their restatement in tests/moments_cases.py, and the kernels are bound by their loads, not by these
@@ -27,18 +28,8 @@
 
 namespace hta {
 
-constexpr int MOM_THREADS = 256;
-constexpr int MOM_SEGMENT_ROWS = 256;     // rows of S per segment when C D fills the machine
-constexpr int MOM_MIN_SEGMENT_ROWS = 32;
-constexpr int MOM_TARGET_BLOCKS = 512;    // shorter segments while the grid has fewer blocks than this
+// MOM_THREADS, the segment constants and moments_segment_rows: moments_rows.hpp (shared with covariance.hip)
 constexpr int MOM_FIN_D = 16, MOM_FIN_C = 16;
-
-static int64_t moments_segment_rows(int64_t S, int64_t C, int64_t D) {
-  const int64_t bx = (C * D + MOM_THREADS - 1) / MOM_THREADS;
-  int64_t R = MOM_SEGMENT_ROWS;
-  while (R > MOM_MIN_SEGMENT_ROWS && bx * ((S + R - 1) / R) < MOM_TARGET_BLOCKS) R /= 2;
-  return R;
-}
 
 // Chan et al.: (na, ma, qa) <- (na, ma, qa) + (nb, mb, qb), nb > 0
 __device__ __forceinline__ void mom_chan(double& na, double& ma, double& qa, double nb, double mb, double qb) {

@@ -31,6 +31,10 @@ cross-chain warm-up takes its diagonal mass from (hamiltorch_amd/adapt.py):
     acc.update(out, skip=1)                                                       # as often as chunks arrive
     m = acc.result(reg_n=5)
     m.mean, m.sd, m.var_within, m.var_between, m.var_total, m.rhat, m.inv_mass
+
+``RunningCovariance`` (csrc/covariance.hip) keeps the off-diagonal too - per chain the co-moments of every pair of coordinates,
+D <= COVARIANCE_MAX_D -, with the same surface; its result has cov_within, cov_total, corr and a [D, D] inv_mass, the dense mass
+of warmup(mass="dense").
 """
 from __future__ import annotations
 
@@ -584,4 +588,209 @@ class RunningMoments:
                                                _abi._stream(self.state)), "hta_moments_finish")
         out = MomentsResult(mean=mean, sd=torch.sqrt(vt), var_within=vw, var_between=vb, var_total=vt, rhat=rh, inv_mass=im,
                             n_draws=int(self.n_draws), n_chains=int(C))
+        return out.to("cpu") if self._host else out
+
+
+# ---- running covariance (csrc/covariance.hip) -------------------------------------------------------------------------------
+#: the largest D of RunningCovariance (include/hamiltorch_amd.h: HTA_COV_MAX_D): the state holds D (D + 1) / 2 co-moments per
+#: chain, 270 MB at 1024 chains and D = 256
+COVARIANCE_MAX_D = 256
+
+
+class CovarianceResult:
+    """Pooled statistics of a RunningCovariance: float64 tensors on the samples' device.  `mean` [D]: the mean of the chain
+    means; `cov_within` [D, D]: the mean over chains of their unbiased covariances; `cov_total` [D, D]: the unbiased covariance
+    of all draws of all chains around `mean`; `sd` = sqrt(diag(cov_total)); `corr` = cov_total / (sd sd^T); `rhat` [D]: R-hat of
+    the unsplit chains; `inv_mass` ([D, D], `dtype`): the regularised `cov_total`, or None when no `reg_n` was given.  The
+    matrices are exactly symmetric; the diagonals, `mean` and `rhat` are MomentsResult's values of the same feed, bit for bit."""
+    __slots__ = ("mean", "sd", "cov_within", "cov_total", "corr", "rhat", "inv_mass", "n_draws", "n_chains")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def max_rhat(self):
+        """max over coordinates of rhat, NaN coordinates ignored."""
+        v = self.rhat[~torch.isnan(self.rhat)]
+        return float(v.max()) if v.numel() else float("nan")
+
+    def to(self, device):
+        return CovarianceResult(**{k: (getattr(self, k).to(device) if torch.is_tensor(getattr(self, k)) else getattr(self, k)) for k in self.__slots__})
+
+    def __repr__(self):
+        return "CovarianceResult(%d draws x %d chains x %d coordinates)" % (self.n_draws, self.n_chains, self.mean.numel())
+
+
+class RunningCovariance:
+    """Per-chain means and co-moments of every pair of coordinates of samples that arrive chunk by chunk, in fp64 on the device
+    (csrc/covariance.hip) - RunningMoments with the off-diagonal kept:
+
+        acc = hamiltorch_amd.diagnostics.RunningCovariance()
+        for _ in range(100):
+            out = hamiltorch_amd.sample(target, start, num_samples=50, ...)
+            acc.update(out, skip=1)
+            start = out[-1]
+        r = acc.result(reg_n=5)
+        r.cov_total, r.corr, r.inv_mass                                             # [D, D]
+
+    `RunningCovariance(C, D, device)` fixes the shape at once; without arguments the first update() does.  D is at most
+    COVARIANCE_MAX_D.  The state is one float64 buffer - `means` [C, D] followed by `comoments` [C, T], T = D (D + 1) / 2, the
+    pairs i <= j packed row-major - and the host integer `n_draws`.  CPU samples are staged to the GPU, and the results of an
+    accumulator fed from the CPU come back on the CPU."""
+
+    def __init__(self, C=None, D=None, device=None):
+        self.state, self.n_draws, self._host, self._shape = None, 0, False, None
+        if (C is None) != (D is None):
+            raise ValueError("RunningCovariance: give both C and D, or neither")
+        if C is not None:
+            if int(C) < 1 or int(D) < 1:
+                raise ValueError("RunningCovariance: bad shape (C=%d D=%d)" % (C, D))
+            self._check_d(int(D))
+            dev = torch.device("cuda" if device is None else device)
+            self._host = dev.type != "cuda"
+            if self._host:
+                from .host import _device
+                dev = _device()
+            self._allocate(int(C), int(D), dev, zero=True)
+
+    @staticmethod
+    def _check_d(D):
+        if D > COVARIANCE_MAX_D:
+            raise ValueError("RunningCovariance: D=%d is beyond the limit of %d coordinates (COVARIANCE_MAX_D)" % (D, COVARIANCE_MAX_D))
+
+    def _allocate(self, C, D, dev, zero=False):
+        self._shape = (C, D)
+        n = C * (D + D * (D + 1) // 2)
+        self.state = (torch.zeros if zero else torch.empty)(n, dtype=torch.float64, device=dev)
+
+    @property
+    def n_chains(self):
+        return None if self.state is None else self._shape[0]
+
+    @property
+    def n_coordinates(self):
+        return None if self.state is None else self._shape[1]
+
+    @property
+    def means(self):
+        """[C, D] view of the state: the chains' means."""
+        C, D = self._shape
+        return self.state[:C * D].view(C, D)
+
+    @property
+    def comoments(self):
+        """[C, T] view of the state: the chains' co-moments, the pairs i <= j packed row-major."""
+        C, D = self._shape
+        return self.state[C * D:].view(C, -1)
+
+    def reset(self):
+        """Forget every draw (the shape stays)."""
+        self.n_draws = 0
+        return self
+
+    def update(self, samples, skip=0):
+        """Add the rows of `samples` after the first `skip` (the inputs of RunningMoments.update).  Returns self."""
+        x = _as_samples(samples)
+        skip = int(skip)
+        if skip < 0:
+            raise ValueError("RunningCovariance: skip=%d" % skip)
+        S, C, D = x.shape[0] - skip, x.shape[1], x.shape[2]
+        if C < 1 or D < 1:
+            raise ValueError("RunningCovariance: no chains or no coordinates in samples of shape %s" % (tuple(x.shape),))
+        self._check_d(D)
+        if S < 1:
+            return self
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float32)
+        if not x.is_cuda:
+            from .host import _device
+            if self.state is None:
+                self._host = True
+            x = x.to(self.state.device if self.state is not None else _device())
+        _abi.require_device(x, "samples")
+        if self.state is None:
+            self._allocate(C, D, x.device)
+        if (C, D) != self._shape or x.device != self.state.device:
+            raise ValueError("RunningCovariance: samples of %d chains x %d coordinates on %s; the accumulator holds %d x %d on %s"
+                             % (C, D, x.device, self._shape[0], self._shape[1], self.state.device))
+        x = x[skip:]
+        if x.stride(2) != 1 or x.stride(1) < D or x.stride(0) < (C - 1) * x.stride(1) + D:
+            x = x.contiguous()
+        lib = _abi.load()
+        vp = ctypes.c_void_p
+        with torch.cuda.device(x.device):
+            nbytes = int(lib.hta_cov_workspace_bytes(S, C, D))
+            ws = _abi.scratch(x, nbytes, "covariance")
+            _abi._check(getattr(lib, "hta_cov_update_" + _abi._suffix(x))(vp(x.data_ptr()), x.stride(0), x.stride(1), S, C, D, self.n_draws,
+                                                                         vp(self.state.data_ptr()), None if ws is None else vp(ws.data_ptr()), nbytes,
+                                                                         _abi._stream(x)), "hta_cov_update")
+        self.n_draws += S
+        return self
+
+    def merge(self, other):
+        """Add the draws another accumulator of the same chains has seen, chain by chain (Chan's formula; the counts may differ).
+        Returns self."""
+        if other.state is None or other.n_draws == 0:
+            return self
+        if self.state is None:
+            self.state, self._host, self._shape = torch.empty_like(other.state), other._host, other._shape
+        if self._shape != other._shape or self.state.device != other.state.device:
+            raise ValueError("RunningCovariance.merge: %s on %s and %s on %s" % (self._shape, self.state.device, other._shape, other.state.device))
+        if self.n_draws == 0:
+            self.state.copy_(other.state)
+        else:
+            na, nb = float(self.n_draws), float(other.n_draws)
+            D = self._shape[1]
+            iu, ju = torch.triu_indices(D, D, device=self.state.device)
+            delta = other.means - self.means
+            self.comoments.add_(other.comoments).add_(delta[:, iu] * delta[:, ju] * (na * nb / (na + nb)))
+            self.means.add_(delta * (nb / (na + nb)))
+            q = self.comoments
+            q[~torch.isfinite(self.means[:, iu] + self.means[:, ju] + q)] = float("nan")
+            self.means[torch.isnan(q[:, iu == ju])] = float("nan")
+        self.n_draws += other.n_draws
+        return self
+
+    @classmethod
+    def stack(cls, parts):
+        """A new accumulator whose chains are the chains of `parts` side by side (equal draw counts and coordinates).  Of the
+        accumulators of a run's first and last half it is the accumulator of the 2 C half chains: its rhat is split R-hat."""
+        parts = list(parts)
+        if not parts or any(p.state is None for p in parts):
+            raise ValueError("RunningCovariance.stack: an accumulator without a shape")
+        if len({p.n_draws for p in parts}) != 1 or len({(p._shape[1], p.state.device) for p in parts}) != 1:
+            raise ValueError("RunningCovariance.stack: the parts differ in draws, coordinates or device")
+        out = cls()
+        out.state = torch.cat([p.means.reshape(-1) for p in parts] + [p.comoments.reshape(-1) for p in parts])
+        out._shape = (sum(p._shape[0] for p in parts), parts[0]._shape[1])
+        out.n_draws, out._host = parts[0].n_draws, all(p._host for p in parts)
+        return out
+
+    def result(self, reg_n=None, reg_floor=1e-3, dtype=None):
+        """The pooled statistics of the draws seen so far (a CovarianceResult).  With `reg_n` also `inv_mass` [D, D] of `dtype`
+        (default float32): cov_total N / (N + reg_n) + reg_floor reg_n / (N + reg_n) I, N = n_draws x chains (Stan: reg_n = 5)."""
+        if self.state is None or self.n_draws < 1:
+            raise ValueError("RunningCovariance.result: no draws yet")
+        lib = _abi.load()
+        C, D = self._shape
+        dev = self.state.device
+        mean, rh = (torch.empty(D, dtype=torch.float64, device=dev) for _ in range(2))
+        cw, ct = (torch.empty((D, D), dtype=torch.float64, device=dev) for _ in range(2))
+        im = None
+        if reg_n is not None:
+            dtype = torch.float32 if dtype is None else dtype
+            if dtype not in (torch.float32, torch.float64):
+                raise TypeError("RunningCovariance.result: inv_mass in float32 or float64, got %s" % dtype)
+            im = torch.empty((D, D), dtype=dtype, device=dev)
+        vp = ctypes.c_void_p
+        p = lambda t: vp(t.data_ptr())                                           # noqa: E731
+        with torch.cuda.device(dev):
+            _abi._check(lib.hta_cov_finish(C, D, self.n_draws, p(self.state), p(mean), p(cw), p(ct), p(rh),
+                                           0.0 if reg_n is None else float(reg_n), float(reg_floor),
+                                           p(im) if im is not None and im.dtype == torch.float32 else None,
+                                           p(im) if im is not None and im.dtype == torch.float64 else None,
+                                           _abi._stream(self.state)), "hta_cov_finish")
+        sd = torch.sqrt(ct.diagonal())
+        out = CovarianceResult(mean=mean, sd=sd, cov_within=cw, cov_total=ct, corr=ct / (sd[:, None] * sd[None, :]), rhat=rh, inv_mass=im,
+                               n_draws=int(self.n_draws), n_chains=int(C))
         return out.to("cpu") if self._host else out

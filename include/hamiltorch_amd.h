@@ -712,6 +712,43 @@ int hta_moments_finish(int64_t C, int64_t D, int64_t n, const double* state, dou
                        double* var_total, double* rhat, double reg_n, double reg_floor, float* inv_mass_f32, double* inv_mass_f64,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Running covariance of samples that arrive chunk by chunk (symbols added under ABI 17; csrc/covariance.hip): the matrix
+ * counterpart of the running moments - per chain the means and the co-moments q_ij = sum_s (x_si - m_i)(x_sj - m_j) of every
+ * pair of coordinates, in fp64 -, and the source of the warm-up's dense mass (hamiltorch_amd/adapt.py, mass="dense").
+ *
+ *   x            a chunk x[S, C, D], S >= 1, D <= HTA_COV_MAX_D: f32 / f64, the stride rules of hta_diag_*.  All arithmetic is fp64.
+ *   state        hta_cov_state_bytes(C, D) = 8 C (D + T) bytes, T = D (D + 1) / 2, 8-byte aligned, the caller's: mean[C][D], then
+ *                comoment[C][T] with the pairs i <= j packed row-major.  The draws per chain so far, n_prev, are the caller's too
+ *                (n_prev = 0: the state is written, not read).
+ *   update       per chain and pair i <= j, in row order (k = 1, 2, ...): di = x_i - m_i, dj = x_j - m_j, m_i += di / k,
+ *                m_j += dj / k, q_ij += di (x_j - m_j) - on the diagonal the recurrence of hta_moments_update, whose means and M2
+ *                the means and the diagonal equal bit for bit for equal input and chunking -, over the segments of R rows of
+ *                hta_moments_update, merged in segment order and then into the state by Chan's formula:
+ *                q_ij += q_ij,chunk + di dj n S / (n + S) with di = m_i,chunk - m_i.
+ *   workspace    >= hta_cov_workspace_bytes(S, C, D) bytes, 8-byte aligned: the segments' partial results.  0 bytes (the pointer
+ *                may then be NULL) when the chunk is one segment: one launch merges it straight into the state.
+ *   non-finite   a NaN or infinite draw at (c, d) leaves NaN in mean[c][d] and in every co-moment of chain c that involves d, for
+ *                good, and touches nothing else.
+ *   finish       hta_cov_finish: the pooled statistics of the n >= 1 draws per chain in `state`, outputs in device memory, any of
+ *                them NULL: mean[D] = mean of the chain means; cov_within[D, D] = mean over chains of q / (n - 1);
+ *                cov_total[D, D] = (sum_c q_c,ij + n sum_c (m_ci - mean_i)(m_cj - mean_j)) / (n C - 1); rhat[D] as
+ *                hta_moments_finish; inv_mass_f32 / inv_mass_f64[D, D] (at most one; needs reg_n, reg_floor >= 0) =
+ *                cov_total N / (N + reg_n) + reg_floor reg_n / (N + reg_n) I, N = n C.  The matrices are written full and exactly
+ *                symmetric; their diagonals, mean and rhat equal hta_moments_finish's outputs bit for bit.
+ *   determinism  no floating-point atomics; every sum runs in an order fixed by (S, C, D).
+ * Bad shapes (D > HTA_COV_MAX_D among them), NULL pointers, overlapping strides and short workspaces return HTA_ERR_INVALID
+ * before any launch; the size queries return -1.  hta_last_route() names the update kernel ("cov_update_kernel<float>"). */
+#define HTA_COV_MAX_D 256 /* at 1024 chains the state is then 270 MB */
+int64_t hta_cov_workspace_bytes(int64_t S, int64_t C, int64_t D);
+int64_t hta_cov_state_bytes(int64_t C, int64_t D);
+int hta_cov_update_f32(const float* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, int64_t n_prev, double* state,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int hta_cov_update_f64(const double* x, int64_t stride_s, int64_t stride_c, int64_t S, int64_t C, int64_t D, int64_t n_prev, double* state,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int hta_cov_finish(int64_t C, int64_t D, int64_t n, const double* state, double* mean, double* cov_within, double* cov_total, double* rhat,
+                   double reg_n, double reg_floor, float* inv_mass_f32, double* inv_mass_f64, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
