@@ -1,6 +1,8 @@
 // libhamiltorch_amd.so: ABI version, error channel, device query, tuning knobs.
 #include <stdarg.h>
 #include "common.hpp"
+#include "mlp.hpp"
+#include "netn.hpp"
 #include "rmhmc.hpp"
 
 namespace hta {
@@ -21,14 +23,12 @@ void note_route(const char* fmt, ...) {
 }
 int g_small_chains_per_block = 0;  // 0 = default (64)
 int g_force_general = 0;
-int g_netn_waves = 1;        // csrc/netn_hmc.hip: waves per chain (2 / 4 where they fit; measured slower at 1024 chains)
 int g_gauss_eig = 1;       // small-D identity-mass Gaussian HMC integrates in the eigenbasis of P (0: direct kernel, 2: chain per lane only)
 int g_fill_blocks = 4096;        // grid cap of the pre-draw pass (256-thread blocks, grid-stride)
 int g_quad_max_chains = 65536;   // up to here a chain takes a DPP quad (one eigen-coordinate per lane), beyond a lane
 int g_quad_variant = 7;          // instance of the quad kernel (hmc_gauss_quad_dev.hpp: VAR); 0 = the round-1 instance, 3 = uniform-base addressing + no NaN guard, 7 = + fused row / butterfly block
 extern int g_metric_second, g_metric_bx3, g_metric_sqrtdraw, g_rmhmc_uvc, g_quad_fused, g_quad_producers, g_quad_chunks, g_quad_starve, g_quad_rows, g_quad_local, g_quad_wide, g_quad_rows_wt, g_quad_lead, g_quad_wide_launches, g_quad_prop, g_quad_prop_sweep, g_quad_prop_chains;         // rmhmc_metric_mfma.hip, rmhmc_uvc.hip, hmc_gaussian.hip (the other metric keys and every fused-RMHMC key: rmhmc.hpp)
-int g_mlp_valu = 0;               // 1 = keep the Bayesian-MLP sampler on the VALU kernel (parity tests of both)
-int g_mlp3_route = 1;             // csrc/mlp3_mfma.hip (two wide hidden layers on the matrix cores); 0 = such models stay on the callback path
+// "mlp_valu", "mlp3_route", "netn_waves": mlp.hpp / netn.hpp, defined beside their routes (mlp_hmc.hip, mlp3_mfma.hip, netn_hmc.hip)
 
 // ---- optional HIP-event timing of the dominant kernel of each call (measurement only) -----------
 // hta_set_tuning("profile", N) arms it; every N-th bracketed launch then records a start/stop event pair

@@ -41,6 +41,21 @@ struct DevOnce {
   bool operator!() const { return !f[dev()]; }
   DevOnce& operator=(bool v) { f[dev()] = v; return *this; }
 };
+// Opts the kernel(s) in to 160 KB of dynamic LDS, together, once per device; `entry` is the C entry point the error text names
+template <typename... K> int allow_big_lds(DevOnce& done, const char* entry, K... kernels) {
+  if (!done) {
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...}) {
+      const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e != hipSuccess) { set_error("%s: hipFuncSetAttribute: %s", entry, hipGetErrorString(e)); return HTA_ERR_LAUNCH; }
+    }
+    done = true;
+  }
+  return HTA_OK;
+}
+
+// abi.cpp: optional HIP-event bracket of a call's dominant kernel (tuning key "profile")
+void profile_begin(hipStream_t s);
+void profile_end(hipStream_t s);
 
 // ---- wave64 reductions (DPP via __shfl_xor butterflies) --------------------------------
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {

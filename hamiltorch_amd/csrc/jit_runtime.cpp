@@ -18,8 +18,6 @@
 #include "jit/jit_args.h"
 
 namespace hta {
-void profile_begin(hipStream_t s);      // abi.cpp: optional HIP-event bracket of a call's dominant kernel
-void profile_end(hipStream_t s);
 namespace {
 
 // ---- hipRTC through dlopen: the library loads (and everything that is not the callback compiler works) without it ----

@@ -99,9 +99,26 @@ template <typename T> __device__ __forceinline__ void mlp_point_loss(int loss, T
   }
 }
 
-extern int g_mlp_valu;                                        // tuning key "mlp_valu": 1 = never take the MFMA kernel
+// The checks of the split / trajectory arguments that every deep-net sampler entry makes (mlp_hmc.hip, mlp3_mfma.hip, netn_hmc.hip), over
+// MlpArgs or NetArgs.  who_hmc / who_eval: the entry-point names in the texts ("hta_mlp_hmc" / "hta_mlp_logp_grad"); the texts themselves
+// are pinned by tests/test_gpu_net_args.py.  mass_text: mlp3_mfma.hip words its mass check differently.  Its own check accepted any kind but
+// HTA_MASS_NONE with operands; this one also asks for HTA_MASS_DIAG, which is the same there only because mlp3_mfma()'s sole caller,
+// netn_hmc(), reaches it after mlp3_eligible(), and that admits an identity or diagonal mass alone.
+template <typename A>
+int check_split_args(const A& a, const char* who_hmc, const char* who_eval,
+                     const char* mass_text = "only identity / diagonal inv_mass are supported natively") {
+  HTA_REQUIRE(a.M >= 1 && a.Nb >= 1 && (int64_t)a.M * a.Nb <= a.N, "%s: M=%d splits of Nb=%d points exceed N=%d", who_hmc, a.M, a.Nb, a.N);
+  HTA_REQUIRE(a.mass_kind == HTA_MASS_NONE || (a.mass_kind == HTA_MASS_DIAG && a.inv_mass && a.mass_factor), "%s: %s", who_hmc, mass_text);
+  if (a.n_traj > 0) HTA_REQUIRE(a.theta_init && a.L >= 0, "%s: bad trajectory arguments", who_hmc);
+  if (a.n_traj == 0) HTA_REQUIRE(a.eval_split >= 0 && a.eval_split < a.M, "%s: split %d not in [0, %d)", who_eval, a.eval_split, a.M);
+  HTA_REQUIRE(a.integ >= HTA_SPLIT_SYMMETRIC && a.integ <= HTA_SPLIT_KMID, "%s: unknown integrator %d", who_hmc, a.integ);
+  HTA_REQUIRE(a.integ != HTA_SPLIT_RAND || a.M <= 64, "%s: SPLITTING_RAND supports at most 64 subsets natively (M=%d)", who_hmc, a.M);
+  HTA_REQUIRE(a.integ != HTA_SPLIT_KMID || a.M >= 2, "%s: SPLITTING_KMID needs at least 2 subsets", who_hmc);
+  return HTA_OK;
+}
+
+extern int g_mlp_valu;                                        // tuning key "mlp_valu" (default 0; defined in mlp_hmc.hip): 1 = never take the MFMA kernel
 bool mlp_mfma_eligible(const MlpArgs<float>& a);
 int mlp_mfma(const MlpArgs<float>& a, hipStream_t s);         // mlp_mfma.hip
-
 
 }  // namespace hta

@@ -18,17 +18,11 @@
 //   db1, dw2, db2, sum r^2: in-lane sums over the tile registers, then two cross-group shuffles.
 // The activations of a point chunk (<= 128 points) stay in registers between the passes: no chunk matrix in LDS,
 // two barriers per chunk, and per-wave state of 3 + NK registers per record.
+//
+// This file: eligibility, the launcher and the instance dispatch.  The kernel, its chunk size and LDS sizing: mlp_mfma_dev.hpp.
 #include "mlp_mfma_dev.hpp"
 
-#if HTA_TIMING
-__device__ unsigned long long hta_dbg[16];
-extern "C" void hta_dbg_read(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(hta_dbg), sizeof(hta_dbg)); }
-#endif
-
 namespace hta {
-
-void profile_begin(hipStream_t s);
-void profile_end(hipStream_t s);
 
 bool mlp_mfma_eligible(const MlpArgs<float>& a) {
   // Gaussian likelihood only: the other likelihoods run on the VALU kernel (mlp_hmc.hip).  Their exp / log1p sequences - even
@@ -45,12 +39,7 @@ template <int NK, int NPT, int ACT, int NTMAX> static int launch_mfma(const MlpA
   int Npad;
   const size_t lds = mfma_lds_bytes(a, NK, NU, 1, &Npad);
   static DevOnce done;
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_mfma_kernel<NK, NPT, ACT, NTMAX, 1>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { set_error("hta_mlp_hmc: hipFuncSetAttribute: %s", hipGetErrorString(e)); return HTA_ERR_LAUNCH; }
-    done = true;
-  }
+  if (const int rc = allow_big_lds(done, "hta_mlp_hmc", &mlp_mfma_kernel<NK, NPT, ACT, NTMAX, 1>)) return rc;
   const int grid = (int)(a.C < 8192 ? a.C : 8192);
   profile_begin(s);
   note_route("mlp_mfma_kernel<%d,%d,%d,%d>", NK, NPT, ACT, NTMAX);

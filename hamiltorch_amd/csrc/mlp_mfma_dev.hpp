@@ -11,53 +11,17 @@
 // in-order wave issues the two chains' instructions one after the other, two waves issue matrix and vector instructions in the same
 // cycle.  What the rewrite did leave behind: the backward pass's four X operands loaded ahead of its four matrix instructions
 // (NC = 1: 6.25 -> 6.13 ms, +2 %).
+//
+// The generality stays.  Turning the [NC] arrays into scalars, with the template signature unchanged, was tried: it changes the
+// -DHTA_MLP_SINGLE instance mlp_mfma_kernel<2,7,0,512,1>, BASELINE config 4's kernel - 226 of about 6 850 assembly lines differ,
+// with identical register, spill and scratch counts (128 VGPR, 56 spilled, 212 bytes) but the spills placed differently in the
+// stage bookkeeping.  That kernel sits at its 128-register cap: such a change needs a timing study of its own.
 #pragma once
 #include "mlp.hpp"
+#include "net_dev.hpp"
 #include "philox.hpp"
 
-#ifndef HTA_TIMING
-#define HTA_TIMING 0   // developer cycle counters per phase of a gradient (wave 0 of block 0), read by tools/scratch/mlp_ablate.cpp
-#endif
-#if HTA_TIMING
-extern __device__ unsigned long long hta_dbg[16];
-#define HTA_TICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[k] += now_ - tlast; tlast = now_; } while (0)
-#else
-#define HTA_TICK(k) do {} while (0)
-#endif
-
 namespace hta {
-
-typedef float V4f __attribute__((ext_vector_type(4)));
-
-template <int CTRL> __device__ __forceinline__ float dpp_get(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-// DPP controls: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_ror:4, row_ror:8
-#define HTA_DPP_X1 0xB1
-#define HTA_DPP_X2 0x4E
-#define HTA_DPP_ROR4 0x124
-#define HTA_DPP_ROR8 0x128
-
-// sum over the 4 lane groups (g); every lane gets the total
-__device__ __forceinline__ float groups_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
-template <int ACT> __device__ __forceinline__ float mact(float z) {
-  // max(z, 0) in ONE VALU op, v_med3_f32(z, 0, FLT_MAX): fmaxf - and med3 against +inf, which the compiler folds into it -
-  // compile to v_max(z, z) (a canonicalize) + v_max(0, .): 56 instead of 28 instructions per gradient at BASELINE config 4.
-  // (An activation of +inf - a diverged chain - becomes FLT_MAX: the log-probability still overflows, the proposal is rejected.)
-  if (ACT == 0) return __builtin_amdgcn_fmed3f(z, 0.0f, 3.4028234663852886e38f);
-  if (ACT == 1) return tanhf(z);
-  return 1.0f / (1.0f + expf(-z));
-}
-template <int ACT> __device__ __forceinline__ float mact_deriv(float h) {
-  if (ACT == 0) return h > 0.0f ? 1.0f : 0.0f;
-  if (ACT == 1) return 1.0f - h * h;
-  return h * (1.0f - h);
-}
 
 template <int NK, int NPT, int ACT, int NC>
 struct MfmaChain {
@@ -68,9 +32,6 @@ struct MfmaChain {
   const float* Xs; const float* Ys; const float* ones; float* fpart; float* rbuf; float* red; float* dump;
   int tid, nthr, NU, t, c, g, kb;
   bool uvalid, wvalid[NK], ones_lane;
-#if HTA_TIMING
-  unsigned long long tacc[16] = {0}, tlast = 0;
-#endif
   __device__ MfmaChain(const MlpArgs<float>& a_) : a(a_) {}
 
   // per chain: the sum over the workgroup (the same two barriers and the same left-to-right sum over the tiles as with one chain)
@@ -106,7 +67,6 @@ struct MfmaChain {
     for (int c0 = lo; c0 < hi; c0 += CP) {
       const int cnt = min(CP, hi - c0);               // a ragged last chunk runs all NPT tiles; its extra points get delta = 0
       V4f h[NC][NPT];
-      HTA_TICK(0);
       // ---- forward: pre-activations of this wave's 16 units at every point of the chunk, then the activations and this
       //      tile's share of f(x_p) = sum_u w2_u h[p, u]: a reduce-scatter over the quad (the 4 point registers end up one
       //      per lane), then rotations by 4 and 8 across the 16 unit lanes.  Straight-line code: tile pt + 1's MFMAs are in
@@ -135,7 +95,7 @@ struct MfmaChain {
         for (int k = 0; k < NC; ++k) {
           float fp[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) { h[k][pt][e] = mact<ACT>(h[k][pt][e]); fp[e] = q[k].w2 * h[k][pt][e]; }
+          for (int e = 0; e < 4; ++e) { h[k][pt][e] = act_fn_med3(ACT, h[k][pt][e]); fp[e] = q[k].w2 * h[k][pt][e]; }
           const float s01 = (odd ? fp[1] : fp[0]) + dpp_get<HTA_DPP_X1>(odd ? fp[0] : fp[1]);
           const float s23 = (odd ? fp[3] : fp[2]) + dpp_get<HTA_DPP_X1>(odd ? fp[2] : fp[3]);
           float sq = (bit1 ? s23 : s01) + dpp_get<HTA_DPP_X2>(bit1 ? s01 : s23);
@@ -144,9 +104,7 @@ struct MfmaChain {
           fw[k * fstride + 16 * pt] = sq;
         }
       }
-      HTA_TICK(1);
       __syncthreads();
-      HTA_TICK(2);
       // ---- once per point and chain: delta_p = -tau_out r_p (GRAD) or r_p, with r_p = b2 + sum_tiles - y_p; 0 beyond the chunk
       for (int i = tid; i < NC * CP; i += nthr) {
         const int k = (NC > 1 && i >= CP) ? 1 : 0, ip = i - k * CP;
@@ -162,9 +120,7 @@ struct MfmaChain {
         const float r = f - Ys[c0 + ip];
         rbuf[i] = (ip < cnt) ? (GRAD ? -a.tau_out * r : r) : 0.0f;
       }
-      HTA_TICK(3);
       __syncthreads();
-      HTA_TICK(4);
       // ---- backward (scalar f32 VALU on purpose: packed f32 ops are slow beside MFMAs)
       const float* xb = ones_lane ? ones : Xs + (size_t)(c0 + 4 * g) * INP + kb;
 #pragma unroll
@@ -181,7 +137,7 @@ struct MfmaChain {
               sdv[k][e] += dl[k][e];
               gw2v[k][e] = fmaf(dl[k][e], h[k][pt][e], gw2v[k][e]);
               if (ACT == 0) bop[k][e] = h[k][pt][e] > 0.0f ? dl[k][e] : 0.0f;
-              else bop[k][e] = dl[k][e] * mact_deriv<ACT>(h[k][pt][e]);
+              else bop[k][e] = dl[k][e] * act_deriv<float>(ACT, h[k][pt][e]);
               if (NK == 4) gb1v[k] += bop[k][e];
             }
           const float x0 = xb[(16 * pt + 0) * INP], x1 = xb[(16 * pt + 1) * INP], x2 = xb[(16 * pt + 2) * INP], x3 = xb[(16 * pt + 3) * INP];
@@ -203,7 +159,6 @@ struct MfmaChain {
         }
       }
     }
-    HTA_TICK(5);
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
       ret[k] = 0;
@@ -223,7 +178,6 @@ struct MfmaChain {
         ret[k] = groups_sum((ssev[k][0] + ssev[k][1]) + (ssev[k][2] + ssev[k][3]));
       }
     }
-    HTA_TICK(6);
   }
 
   // d log p_m / d theta over points [lo, hi) + prior / prior_scale  (S:1156)
@@ -406,9 +360,6 @@ __global__ __launch_bounds__(NTMAX, NC == 1 ? 4 : 2) void mlp_mfma_kernel(MlpArg
       continue;
     }
 
-#if HTA_TIMING
-    ch.tlast = __builtin_readcyclecounter();
-#endif
     float lp_cur[NC];
     ch.logp_total(cur, lp_cur);
     int32_t rejected[NC];
@@ -505,9 +456,6 @@ __global__ __launch_bounds__(NTMAX, NC == 1 ? 4 : 2) void mlp_mfma_kernel(MlpArg
       store_rec(a.theta + cidx[k] * D, cur[k]);
       if (tid == 0 && a.reject_count) a.reject_count[cidx[k]] += rejected[k];
     }
-#if HTA_TIMING
-    if (tid == 0 && blockIdx.x == 0) for (int k = 0; k < 16; ++k) hta_dbg[k] = ch.tacc[k];
-#endif
   }
 }
 

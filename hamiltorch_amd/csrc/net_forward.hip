@@ -138,11 +138,7 @@ int net_forward(const T* theta, int64_t S, int n_layers, const int* dims, int ac
               FW_MAXW, FW_MAXO);
   const size_t lds = (size_t)2 * wmax * FW_TPB * sizeof(T);
   static DevOnce done;
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&net_forward_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e)); return HTA_ERR_LAUNCH; }
-    done = true;
-  }
+  if (const int rc = allow_big_lds(done, who, &net_forward_kernel<T>)) return rc;
   const dim3 grid((unsigned)((N + FW_TPB - 1) / FW_TPB), (unsigned)(S < 32768 ? S : 32768));
   note_route("net_forward_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
   net_forward_kernel<T><<<grid, FW_TPB, lds, s>>>(theta, S, (int)D, n_layers, d, act, X, N, out, wmax);

@@ -24,8 +24,10 @@ template <typename T> struct NetArgs {
   void* workspace; int64_t workspace_bytes;     // ABI 10: caller-owned scratch (hta_netn_hmc_workspace_bytes; mlp3 route: the momentum slots)
 };
 
+extern int g_netn_waves;                                      // tuning key "netn_waves" (default 1; defined in netn_hmc.hip)
+
 // csrc/mlp3_mfma.hip: Linear(n_in, H1)-act-Linear(H1, H2)-act-Linear(H2, 1), Gaussian likelihood, fp32, H1, H2 <= 104
-extern int g_mlp3_route;                                      // tuning key "mlp3_route" (default 1)
+extern int g_mlp3_route;                                      // tuning key "mlp3_route" (default 1; defined in mlp3_mfma.hip)
 bool mlp3_eligible(const NetArgs<float>& a);
 int mlp3_mfma(const NetArgs<float>& a, hipStream_t s);
 int64_t mlp3_workspace_bytes(int64_t C, int n_layers, const int* dims);     // 0 = these shapes never take the matrix-core route

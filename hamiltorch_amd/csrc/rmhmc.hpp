@@ -53,9 +53,6 @@ template <typename T>
 int mh_select(T* cur, const T* prop, const T* init, const T* Ho, const T* Hn, const T* lpn, T* row, int32_t* rej,
               uint8_t* acc, int64_t C, int D, int n, int burn, uint64_t seed, uint64_t off, hipStream_t s);
 
-void profile_begin(hipStream_t s);
-void profile_end(hipStream_t s);
-
 // rmhmc_fused.hip: the identity-soft-abs fast path of the Gaussian-target sampler (its tuning keys are defined at the top of that file)
 extern int g_rmhmc_fused;                                   // tuning key "rmhmc_fused" (default 1)
 extern int g_rmhmc_batch;                                   // tuning key "rmhmc_batch" (default 1)

@@ -102,17 +102,7 @@ static int fused_cu_count() {
   return cus[dev];
 }
 
-// Opts the kernels in to 160 KB of dynamic LDS, together, once per device
-template <typename... K> static int allow_big_lds(DevOnce& done, K... kernels) {
-  if (!done) {
-    for (const void* k : {reinterpret_cast<const void*>(kernels)...}) {
-      const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) { set_error("hta_rmhmc_gaussian_sample: hipFuncSetAttribute: %s", hipGetErrorString(e)); return HTA_ERR_LAUNCH; }
-    }
-    done = true;
-  }
-  return HTA_OK;
-}
+static constexpr const char* kEntry = "hta_rmhmc_gaussian_sample";     // the entry point allow_big_lds' error text names
 
 // the one-chain kernels' instance of the register slice: f(std::integral_constant<int, KH>{}) for KH = 8, 16 ... 64
 template <typename F> static int with_kh(int KH, F&& f) {
@@ -187,8 +177,8 @@ int rmhmc_fused_sample(T* cur, const T* theta_init, const T* P, const T* Sinv, c
     T* const p_blk = (ov && (bidx & 1)) ? p_ws + (int64_t)block * per_traj : p_ws;
     if (block > 0) {
       static DevOnce done_mom, done_split;     // per T instantiation
-      if (draw == Draw::workgroup) { if (const int rc = allow_big_lds(done_mom, &rmhmc_momentum_kernel<T>)) return rc; }
-      if (draw == Draw::split) { if (const int rc = allow_big_lds(done_split, &rmhmc_momentum_split_kernel<T>)) return rc; }
+      if (draw == Draw::workgroup) { if (const int rc = allow_big_lds(done_mom, kEntry, &rmhmc_momentum_kernel<T>)) return rc; }
+      if (draw == Draw::split) { if (const int rc = allow_big_lds(done_split, kEntry, &rmhmc_momentum_split_kernel<T>)) return rc; }
       const int64_t ntask = (int64_t)nt * C;
       const int toff = traj_offset + t0;
       // with the overlap: on the side stream, once the trajectories of block b-2 are done with this half, and `s` waits for the draws
@@ -264,8 +254,8 @@ int rmhmc_fused_sample(T* cur, const T* theta_init, const T* P, const T* Sinv, c
           return with_track([&](auto TRACK) -> int {
             constexpr bool TR = decltype(TRACK)::value;
             static DevOnce done_b;                               // the four instances opt in together
-            if (const int rc = allow_big_lds(done_b, &rmhmc_batch_kernel<25, true>, &rmhmc_batch_kernel<28, true>, &rmhmc_batch_kernel<25, false>,
-                                             &rmhmc_batch_kernel<28, false>))
+            if (const int rc = allow_big_lds(done_b, kEntry, &rmhmc_batch_kernel<25, true>, &rmhmc_batch_kernel<28, true>,
+                                             &rmhmc_batch_kernel<25, false>, &rmhmc_batch_kernel<28, false>))
               return rc;
             profile_begin(s);
             note_route("rmhmc_batch_kernel<%d,%s>", D <= 100 ? 25 : 28, TR ? "true" : "false");
@@ -281,7 +271,7 @@ int rmhmc_fused_sample(T* cur, const T* theta_init, const T* P, const T* Sinv, c
             constexpr bool TR = decltype(TRACK)::value;
             static DevOnce done_w[2];                            // per instance
             const auto wide = KH == 56 ? &rmhmc_fused_kernel_wide<56, TR> : &rmhmc_fused_kernel_wide<64, TR>;
-            if (const int rc = allow_big_lds(done_w[KH == 64], wide)) return rc;
+            if (const int rc = allow_big_lds(done_w[KH == 64], kEntry, wide)) return rc;
             profile_begin(s);
             note_route("rmhmc_fused_kernel_wide<%d,%s>", KH, TR ? "true" : "false");
             wide<<<grid, FNT, fused_lds_bytes<T>(D, nullptr, 1, need_w), s>>>(a, ld, need_w ? 1 : 0);
@@ -296,7 +286,7 @@ int rmhmc_fused_sample(T* cur, const T* theta_init, const T* P, const T* Sinv, c
           constexpr auto kern = &rmhmc_fused_kernel<T, decltype(KHC)::value, 1, decltype(TRACK)::value>;
           constexpr auto kern2 = &rmhmc_fused_kernel<T, decltype(KHC)::value, 2>;
           static DevOnce done, done2;
-          if (const int rc = pair ? allow_big_lds(done2, kern2) : allow_big_lds(done, kern)) return rc;
+          if (const int rc = pair ? allow_big_lds(done2, kEntry, kern2) : allow_big_lds(done, kEntry, kern)) return rc;
           profile_begin(s);
           if (pair) {
             const int64_t npair = (C + 1) / 2;

@@ -414,11 +414,7 @@ template <typename T> int metric_eval(const MetricArgsT<T>& a, hipStream_t s) {
     vws = static_cast<T*>(a.workspace);
   }
   auto launch = [&](auto kern, DevOnce& done) -> int {
-    if (!done) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) { set_error("hta_metric_eval: hipFuncSetAttribute: %s", hipGetErrorString(e)); return HTA_ERR_LAUNCH; }
-      done = true;
-    }
+    if (const int rc = allow_big_lds(done, "hta_metric_eval", kern)) return rc;
     profile_begin(s);
     note_route("metric_eval_kernel<%s%s>", sizeof(T) == 4 ? "float" : "double", g.dyn ? ",aglobal,dyn" : g.aglobal ? ",aglobal" : (g.vglobal ? ",vglobal" : ""));
     kern<<<grid, MT, g.lds, s>>>(k, g.ne, g.lda, g.ldv, g.v0_lds, vws);

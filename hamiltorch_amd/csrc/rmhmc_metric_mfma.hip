@@ -183,11 +183,7 @@ static int metric_launch_prepare(const MetricArgsT<float>& a, const void* kernel
   HTA_REQUIRE(p.lds <= 160 * 1024, "%s: D=%d does not fit the LDS", what, a.D);
   p.k = a;
   if (p.k.max_sweeps <= 0) p.k.max_sweeps = 16;
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { set_error("%s: hipFuncSetAttribute: %s", entry, hipGetErrorString(e)); return HTA_ERR_LAUNCH; }
-    done = true;
-  }
+  if (const int rc = allow_big_lds(done, entry, kernel)) return rc;
   p.grid = (int)(a.B < 65536 ? a.B : 65536);
   return HTA_OK;
 }

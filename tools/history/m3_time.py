@@ -1,3 +1,4 @@
+# RETIRED with the M3_TIMING switch of mlp3_mfma.hip: 78844e1 is the last commit whose source builds with -DM3_TIMING=1 (the cycle counters hta_m3_dbg_read returns).
 """Developer cycle attribution of mlp3_mfma_kernel (wave 0 of workgroup 0 = chain 0): needs tools/scratch/m3_time.sh's build."""
 import sys, os, ctypes, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,4 +1,5 @@
 #!/bin/bash
+# RETIRED with the M3_TIMING switch of mlp3_mfma.hip: 78844e1 is the last commit whose source builds with -DM3_TIMING=1 (paths below as they were under tools/scratch/).
 # builds the timing variant of the library (mlp3_mfma.hip with -DM3_TIMING=1, the other objects as built)
 set -e
 cd "$(dirname "$0")/../../hamiltorch_amd/csrc"

@@ -1,3 +1,4 @@
+// RETIRED with the HTA_ABL / HTA_TIMING switches of mlp_hmc.hip and mlp_mfma.hip: 78844e1 is the last commit whose source builds with them (and exports hta_dbg_read).
 // Developer harness: times hta_mlp_hmc_sample_f32 on the BASELINE config-4 shape with parts of the
 // kernel compiled out (-DHTA_ABL=bits, see mlp_hmc.hip).  Built and run by tools/scratch/mlp_ablate.sh.
 #include <hip/hip_runtime.h>

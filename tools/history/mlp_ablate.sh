@@ -1,4 +1,5 @@
 #!/bin/bash
+# RETIRED with the HTA_ABL switch of mlp_hmc.hip: 78844e1 is the last commit whose source builds with -DHTA_ABL=bits (paths below as they were under tools/scratch/).
 # usage: tools/scratch/mlp_ablate.sh build   (here)   |   tools/scratch/mlp_ablate.sh run   (on the GPU box)
 cd "$(dirname "$0")/../.."
 OUT=tools/scratch/_abl

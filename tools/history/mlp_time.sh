@@ -1,4 +1,5 @@
 #!/bin/bash
+# RETIRED with the HTA_TIMING switch of mlp_mfma.hip: 78844e1 is the last commit whose source builds with -DHTA_TIMING=1 (paths below as they were under tools/scratch/).
 # builds the cfg4 phase-timing harness: tools/scratch/_abl/mlp_plain (the library as built) and mlp_t (mlp_mfma.hip with
 # -DHTA_TIMING=1: s_memtime stamps of wave 0 at the phase boundaries of a gradient)
 set -e

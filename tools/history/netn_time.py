@@ -1,3 +1,4 @@
+# RETIRED with the NETN_TIMING switch of netn_hmc.hip: 78844e1 is the last commit whose source builds with -DNETN_TIMING=1 (the cycle counters hta_netn_dbg_read returns).
 """Developer cycle attribution of netn_hmc_kernel (workgroup 0 = chain 0): needs tools/scratch/netn_time.sh's build."""
 import sys, os, ctypes, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

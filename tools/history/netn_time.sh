@@ -1,4 +1,5 @@
 #!/bin/bash
+# RETIRED with the NETN_TIMING switch of netn_hmc.hip: 78844e1 is the last commit whose source builds with -DNETN_TIMING=1 (paths below as they were under tools/scratch/).
 # builds the timing variant of the library (netn_hmc.hip with -DNETN_TIMING=1, the other objects as built)
 set -e
 cd "$(dirname "$0")/../../hamiltorch_amd/csrc"
